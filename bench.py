@@ -17,10 +17,16 @@ ranks). This is the mode the path scales in: its time is set by per-block chains
 is never shorter than its slowest block's chains, so this mode cannot go much above 1x for the chain-bound configurations; it is kept
 for the configurations that are not (--config lz, huffman, ans0).
 
-Also on the line (N=1): roofline of the dominant KERNEL (HIP-event time of its launches inside the library,
-`knz_last_kernel_times`; HBM traffic from two live rocprofv3 PMC passes of this same command when rocprofv3 is
-present), the PCIe-inclusive rate of the host-pointer batch hook the cgo shim calls (`host_hook_MBps`), and the CPU
-baseline (oracle = C++ restatement of the kanzi-go CPU path, bounded sample).
+Also on the line: roofline of the dominant KERNEL (HIP-event time of its launches inside the library, `knz_last_kernel_times`,
+recorded during the timed steps). A plain run does nothing else: it sets up, warms up, times the steps and prints the line.
+`--full` adds what takes work of its own (N=1): HBM traffic from two live rocprofv3 PMC passes of this same command when
+rocprofv3 is present, the PCIe-inclusive rate of the host-pointer batch hook the cgo shim calls (`host_hook_MBps`), the CPU
+baseline (the reference's own code translated, beside the oracle = C++ restatement of the kanzi-go CPU path, bounded sample),
+the FPAQ stage comparison, and the checks of the timed stream against the oracle (`bit_exact_vs_oracle`) and the reference-written
+stream (`bit_exact_vs_reference`); N>1, strong: the weak-scaling region.
+
+`--dump-outputs DIR` writes what the last timed step handed its caller (the .knz stream, the decoded bytes) as .npy files
+(dump_outputs): the inputs are the same on every run, so two builds can be compared output for output.
 
 Other modes (one JSON object instead of the line): `--handles 1,2,4,8` = K host threads x one handle each at the host-pointer boundary; `--in-process-devices 1,2,4,8
 [--depth N]` = ONE handle of knz_open_devices over K lanes (what Writer / Reader.EnableGPUDevices binds: lane i on device i % devices present, so an 8-GPU box measures one
@@ -476,6 +482,35 @@ def pmc_traffic(argv_child, timeout_s=900):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+DUMP_SAMPLE = 4 << 20    # bytes of an output written as they are (float32: 16 MiB per output)
+DUMP_CHUNK = 1 << 16     # every byte of it also enters the sum of its 64 KiB chunk (float64)
+
+
+def dump_outputs(dirname, outputs):
+    """--dump-outputs: the byte tensors the timed path handed its caller in the last step, as DIR/<name>.npy (float32 byte values: all of them up to
+    DUMP_SAMPLE bytes, else DUMP_SAMPLE positions drawn with a fixed seed, sorted), DIR/<name>_chunk_sums.npy (float64 sums of every DUMP_CHUNK bytes,
+    the last chunk short) and DIR/sizes.npy (float64 byte count of each output, in the order given). Two builds that write the same bytes write the
+    same files; about 33 MB for the two outputs of a step."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    sizes = []
+    for name, t in outputs.items():
+        n = int(t.numel())
+        sizes.append(n)
+        if n > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(20240607).integers(0, n, DUMP_SAMPLE))
+            sample = t[torch.from_numpy(idx).to(t.device)]
+        else:
+            sample = t
+        np.save(os.path.join(dirname, f"{name}.npy"), sample.cpu().numpy().astype(np.float32))
+        full = n - n % DUMP_CHUNK
+        sums = t[:full].view(-1, DUMP_CHUNK).sum(dim=1, dtype=torch.int64)
+        if full < n:
+            sums = torch.cat([sums, t[full:].sum(dtype=torch.int64).view(1)])
+        np.save(os.path.join(dirname, f"{name}_chunk_sums.npy"), sums.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(dirname, "sizes.npy"), np.array(sizes, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -485,7 +520,7 @@ def main():
     ap.add_argument("--config", default="bwt", choices=sorted(CONFIGS))
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"], help="N>1: ONE fixed job (the BASELINE corpus) split over the GPUs (strong, default: the figure BASELINE.json's "
                                                                                     "metric and north_star name; the weak figure rides along as roofline.weak_value_MBps) or one corpus copy per GPU in one stream (weak)")
-    ap.add_argument("--no-weak", action="store_true", help="N>1, strong: skip the second (weak-scaling) timed region")
+    ap.add_argument("--no-weak", action="store_true", help="N>1, strong, --full: skip the second (weak-scaling) timed region")
     ap.add_argument("--size", type=int, default=0, help="override the corpus size (debug; the defaults are the BASELINE sizes: 211957760 / 10^9 for fpaq)")
     ap.add_argument("--block-size", type=int, default=0, help="override the block size (debug)")
     ap.add_argument("--transform", default="", help="override the transform sequence of the config, e.g. LZP or BWT+SRT+ZRLT (debug)")
@@ -502,11 +537,19 @@ def main():
     ap.add_argument("--no-verify", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="skip the two rocprofv3 PMC passes (roofline.traffic = null)")
     ap.add_argument("--no-host-hook", action="store_true", help="skip the PCIe-inclusive host-pointer measurement")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline figure does not need: the bit-exactness checks against the oracle and "
+                                                        "the reference-written stream, the rocprofv3 PMC passes, the host-pointer hook, the CPU baselines, the FPAQ stage "
+                                                        "comparison and (N > 1, strong) the weak-scaling region (each still subject to its --no-* switch)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last step handed its caller (the .knz stream and the "
+                                                                      "decoded bytes) to DIR/<name>.npy as float32 / float64 (a fixed, seeded sample of each plus "
+                                                                      "the sums of its 64 KiB chunks)")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 1 if args.config == "fpaq" else 10
     if args.warmup is None:
         args.warmup = 0 if args.config == "fpaq" else 3
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.handles or args.in_process_devices:
         # several handles = several streams: the HIP runtime multiplexes all streams of a process onto GPU_MAX_HW_QUEUES (default 4) hardware queues and
         # kernels of streams that share a queue run one after the other. libknz_gpu asks for 32 when it is loaded (unless the host chose a value); under
@@ -707,6 +750,10 @@ def main():
     elapsed = timed_region(job)
     size, nblocks, n_my, result, stage, kern_ms, kern_launches = job.size, job.nblocks, job.n_my, job.result, job.stage, job.kern_ms, job.kern_launches
     t_enc, t_dec, d_src, d_seg, d_back, d_stream = job.t_enc, job.t_dec, job.d_src, job.d_seg, job.d_back, job.d_stream
+    if args.dump_outputs and rank == 0:
+        # (N > 1: the assembled stream and rank 0's own decoded blocks)
+        stream_out = (d_seg if not multi else d_stream)[:result["stream_bytes"]]
+        dump_outputs(args.dump_outputs, {"stream": stream_out, "decoded": d_back[:n_my]})
     rank_kernel_max = None
     if multi:
         # the slowest rank's time per kernel: what the SCALE line's shape is made of (a chain kernel is flat in the number of blocks a rank owns)
@@ -722,9 +769,9 @@ def main():
         dist.all_reduce(okt, op=dist.ReduceOp.MIN)
         ok_roundtrip = bool(int(okt.item()))
 
-    # N > 1, strong: the weak-scaling figure (one corpus copy per GPU in one stream) rides along as a second timed region of the same shape
+    # N > 1, strong, --full: the weak-scaling figure (one corpus copy per GPU in one stream) rides along as a second timed region of the same shape
     weak = None
-    if multi and world > 1 and strong and not args.no_weak:
+    if args.full and multi and world > 1 and strong and not args.no_weak:
         wj = make_job(False)
         w_el = timed_region(wj)
         w_ok = bool(torch.equal(wj.d_back[:wj.n_my], wj.d_src[:wj.n_my])) if wj.n_my else True
@@ -805,7 +852,7 @@ def main():
                          "timing": "HIP events around the kernel's launches on the launch stream (knz_last_kernel_times)",
                          "kernel_ms_per_step": {k: round(v / K_, 3) for k, v in sorted(kern_ms.items(), key=lambda kv: -kv[1])[:12]},
                          "kernel_launches_per_step": {k: round(kern_launches[k] / K_, 2) for k, v in sorted(kern_ms.items(), key=lambda kv: -kv[1])[:12]}})
-            if not args.no_pmc and not multi and not emu:
+            if args.full and not args.no_pmc and not multi and not emu:
                 # (fpaq: one 10^9-byte step is ~35 s of two serial chains per block; its counter passes run a single step)
                 child = ["--config", args.config, "--steps", "1" if args.config == "fpaq" else "2", "--warmup", "0" if args.config == "fpaq" else "1",
                          "--no-cpu-baseline", "--no-verify", "--no-pmc", "--no-host-hook"]
@@ -880,7 +927,7 @@ def main():
                 out["fallback_counters_last_batch"] = fb
         if entropy == "FPAQ":
             out["chain_bound"] = True          # one binary arithmetic-coding chain per block by format: flat in the block count
-            if not multi and not emu and not args.no_cpu_baseline:
+            if args.full and not multi and not emu and not args.no_cpu_baseline:
                 try:
                     out["fpaq_stage"] = fpaq_stage_comparison(base, nblocks, kern_ms.get("knz_fpaq_encode_kernel", 0.0) / K_, kern_ms.get("knz_fpaq_decode_kernel", 0.0) / K_, m_local)
                 except Exception as e:   # noqa: BLE001
@@ -889,7 +936,7 @@ def main():
             # the single-launch walk + decode hands a chunk to the serial kernel when a decoder gives up waiting for its walker:
             # 0 for every stream a kanzi encoder wrote unless the dispatch order went against the kernel
             out["huffman_serial_chunks_last_decode"] = int(codec.last_counter(0))
-        if not args.no_verify:
+        if args.full and not args.no_verify:
             import oracle_lib as O
             exp = O.compress(tiled(0, size), transform, entropy, bs, 0, jobs=os.cpu_count() or 1)
             got = (d_seg if not multi else d_stream)[:C_bytes].cpu().numpy().tobytes()
@@ -909,7 +956,7 @@ def main():
                 out["reference_vector_error"] = str(e)
             out["parity_note"] = ("oracle = in-repo C++ restatement of kanzi-go, pinned by oracle/_ref (the reference's own .go sources translated mechanically to C++ and compiled: "
                                   "tests/test_ref_build.py, tests/test_ref_streams.py; DESIGN.md section 2)")
-        if not multi and not emu and not args.no_host_hook:
+        if args.full and not multi and not emu and not args.no_host_hook:
             try:
                 out["host_hook_MBps"] = host_hook_rate(K, (transform, entropy, bs, 0, local_rank), base[:size] if size <= base_size else tiled(0, size), bs)
                 # (the metric of SURVEY 8d "including H2D / D2H": never `value`, kept beside it)
@@ -917,7 +964,7 @@ def main():
                 roof["host_hook_encode_MBps"] = out["host_hook_MBps"]["encode"]; roof["host_hook_decode_MBps"] = out["host_hook_MBps"]["decode"]
             except Exception as e:   # noqa: BLE001
                 out["host_hook_MBps"] = {"error": str(e)}
-        if not args.no_cpu_baseline and not multi:
+        if args.full and not args.no_cpu_baseline and not multi:
             cb = None
             try:
                 import ref_lib

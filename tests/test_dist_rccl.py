@@ -75,7 +75,7 @@ def test_bench_distributed_code_path_on_rccl():
     import json
     root = os.path.dirname(HERE)
     env = dict(os.environ, MASTER_PORT=str(29600 + (os.getpid() % 300)))
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--force-dist", "--steps", "1", "--warmup", "1", "--no-pmc", "--no-cpu-baseline"],
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--force-dist", "--steps", "1", "--warmup", "1", "--full", "--no-pmc", "--no-cpu-baseline"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=850, cwd=root, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

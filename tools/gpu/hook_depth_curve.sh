@@ -2,10 +2,10 @@
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
 O=gpurun_out/r05_hook_depth; mkdir -p $O
 for c in 1 2 4 5; do
-  timeout 900 python bench.py --copies $c --steps 2 --warmup 1 --no-pmc --no-cpu-baseline > $O/bwt_copies_$c.json 2> $O/bwt_copies_$c.err
+  timeout 900 python bench.py --copies $c --steps 2 --warmup 1 --full --no-pmc --no-cpu-baseline > $O/bwt_copies_$c.json 2> $O/bwt_copies_$c.err
 done
 for c in 1 2 4 8; do
-  timeout 900 python bench.py --config l5 --copies $c --steps 2 --warmup 1 --no-pmc --no-cpu-baseline > $O/l5_copies_$c.json 2> $O/l5_copies_$c.err
+  timeout 900 python bench.py --config l5 --copies $c --steps 2 --warmup 1 --full --no-pmc --no-cpu-baseline > $O/l5_copies_$c.json 2> $O/l5_copies_$c.err
 done
 python - <<'PY'
 import json, glob, os

@@ -1,7 +1,7 @@
 #!/bin/bash
 # One script for the GPU box (gpurun -- 'bash tools/gpu/run.sh <step> ...'); every step writes under gpurun_out/ with the prefix $TAG (default r04).
 #   tests[:EXPR]      pytest -m gpu (EXPR = -k expression)
-#   bench[:CONFIG]    bench.py line of a config (bwt = default, lz, huffman, ans0, l5, fpaq) with its live PMC passes, host hook, CPU baseline
+#   bench[:CONFIG]    bench.py --full line of a config (bwt = default, lz, huffman, ans0, l5, fpaq) with its live PMC passes, host hook, CPU baseline, checks
 #   quick[:CONFIG]    bench.py without the slow extras (no CPU baseline / PMC / host hook), 5 steps
 #   trace[:CONFIG]    rocprofv3 --kernel-trace --stats of the quick command -> <TAG>_kernel_stats_<config>.md (+ the suffix sort's per-round timeline)
 #   lib:NAME:FLAGS    (run on the build side) hipcc build of kanzi-go_amd/variants/libknz_NAME.so with extra FLAGS, e.g. lib:measure:-DKNZ_MEASURE
@@ -26,7 +26,7 @@ for step in "$@"; do
     lib) name=${arg%%:*}; flags=${arg#*:}; mkdir -p kanzi-go_amd/variants
          /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -Wno-unused-variable -Wno-unused-value $flags -o kanzi-go_amd/variants/libknz_$name.so kanzi-go_amd/csrc/knz_gpu.hip 2>&1 | grep -i "error"; echo "lib $name done";;
     tests) timeout 2400 python -m pytest tests -m gpu -x -q ${arg:+-k "$arg"} --durations=6 > gpurun_out/${TAG}_pytest.log 2>&1; echo "pytest rc=$?"; tail -10 gpurun_out/${TAG}_pytest.log;;
-    bench) c=${arg:-bwt}; extra=""; [ $c = fpaq ] && extra="--steps 1 --warmup 0 --no-host-hook"
+    bench) c=${arg:-bwt}; extra="--full"; [ $c = fpaq ] && extra="--full --steps 1 --warmup 0 --no-host-hook"
          timeout 3000 python bench.py --config $c $extra > gpurun_out/${TAG}_bench_$c.json 2> gpurun_out/${TAG}_bench_$c.err; echo "bench $c rc=$?"; line gpurun_out/${TAG}_bench_$c.json; tail -2 gpurun_out/${TAG}_bench_$c.err;;
     quick) c=${arg:-bwt}; timeout 900 python bench.py --config $c --no-cpu-baseline --no-pmc --no-host-hook --steps 5 --warmup 2 > gpurun_out/${TAG}_quick_$c.json 2> gpurun_out/${TAG}_quick_$c.err; echo "quick $c rc=$?"; line gpurun_out/${TAG}_quick_$c.json
          grep "suffix sort" gpurun_out/${TAG}_quick_$c.err | head -8;;
