@@ -2,7 +2,7 @@
 // whole batch of blocks. Every stage runs for all blocks at once; a block whose stage declines (Forward error) keeps its
 // previous bytes and its skip bit (Sequence.go:86-91); applied blocks ping-pong between two device regions.
 
-static bool transform1_on_device(uint32_t t) { return t == KNZ_T_NONE || t == KNZ_T_BWT || t == KNZ_T_RANK || t == KNZ_T_MTFT || t == KNZ_T_ZRLT || t == KNZ_T_LZ || t == KNZ_T_LZX || t == KNZ_T_SRT || t == KNZ_T_LZP || t == KNZ_T_UTF || t == KNZ_T_TEXT; }
+static bool transform1_on_device(uint32_t t) { return t == KNZ_T_NONE || t == KNZ_T_BWT || t == KNZ_T_RANK || t == KNZ_T_MTFT || t == KNZ_T_ZRLT || t == KNZ_T_LZ || t == KNZ_T_LZX || t == KNZ_T_SRT || t == KNZ_T_LZP || t == KNZ_T_UTF || t == KNZ_T_TEXT || t == KNZ_T_PACK || t == KNZ_T_DNA; }
 
 static int seq_tokens(uint64_t t, uint32_t out[8]) {            // transform.New (Factory.go:58-95)
     int n = 0;
@@ -788,6 +788,45 @@ static int lz_inverse_par(Handle* h, XfBatch& x, const LzArgs& la, hipStream_t s
     return KNZ_OK;
 }
 
+// ---- PACK / DNA (alias.hip) -------------------------------------------------------------------------------------------------
+// Bounded groups of blocks like the UTF stage: the forward stage keeps a 65536-bin pair histogram per block (256 KiB), so the workspace is
+// sized to a group of at most 64 blocks (16 MiB), not to the batch.
+static int alias_stage(Handle* h, XfBatch& x, bool onlyDna, bool forward, hipStream_t st) {
+    const uint32_t nb = x.nblocks;
+    const uint32_t G = std::min<uint32_t>(nb, 64u);
+    if (h->alias_state.reserve((size_t)G * KNZ_ALIAS_STATE_WORDS * 4) || (forward && h->alias_f1.reserve(((size_t)G << 16) * 4)))
+        return knz_set_error(h, forward ? KNZ_ERR_CREATE_COMPRESSOR : KNZ_ERR_CREATE_DECOMPRESSOR, "device workspace allocation failed (PACK)");
+    const uint32_t cap = (uint32_t)std::min<uint64_t>(x.stride, 0xFFFFFFFFu);
+    for (uint32_t g0 = 0; g0 < nb; g0 += G) {
+        const uint32_t gn = std::min<uint32_t>(G, nb - g0);
+        AliasArgs a;
+        a.nblocks = gn; a.segs_per_block = x.spb; a.in_ptr = x.cur_ptr + g0; a.in_len = x.cur_len + g0; a.out_ptr = x.out_ptr + g0; a.out_cap = cap;
+        a.out_len = x.out_len + g0; a.ok = x.ok + g0; a.active = x.active + g0; a.blk_dt = (forward && x.blk_dt) ? x.blk_dt + g0 : nullptr;
+        a.state = h->alias_state.as<uint32_t>(); a.f1 = h->alias_f1.as<uint32_t>(); a.seg = h->xf_sega.as<uint32_t>() + (size_t)g0 * x.spb * 4;
+        a.only_dna = onlyDna ? 1u : 0u;
+        a.h1_chunks = (uint32_t)std::max<uint64_t>(1, ((uint64_t)cap + KNZ_ALIAS_H1_CHUNK - 1) / KNZ_ALIAS_H1_CHUNK);
+        HIP_OK(hipMemsetAsync(h->alias_state.p, 0, (size_t)gn * KNZ_ALIAS_STATE_WORDS * 4, st));
+        const dim3 gseg(x.spb, gn);
+        if (forward) {
+            HIP_OK(hipMemsetAsync(h->alias_f1.p, 0, ((size_t)gn << 16) * 4, st));
+            KNZ_LAUNCH_PROBED(knz_alias_hist0_kernel, gseg, dim3(256), 0, st, a);
+            hipLaunchKernelGGL(knz_alias_plan_kernel, dim3(gn), dim3(256), 0, st, a);
+            KNZ_LAUNCH_PROBED(knz_alias_hist1_kernel, dim3(KNZ_ALIAS_SLICES * a.h1_chunks, gn), dim3(KNZ_ALIAS_H1_THREADS), 0, st, a);
+            KNZ_LAUNCH_PROBED(knz_alias_select_kernel, dim3(gn), dim3(1024), 0, st, a);
+            KNZ_LAUNCH_PROBED(knz_alias_pack_kernel, gseg, dim3(256), 0, st, a);
+            KNZ_LAUNCH_PROBED(knz_alias_parse_kernel<false>, gseg, dim3(256), 0, st, a);
+            hipLaunchKernelGGL(knz_alias_offsets_kernel, dim3(gn), dim3(64), 0, st, a);
+            KNZ_LAUNCH_PROBED(knz_alias_parse_kernel<true>, gseg, dim3(256), 0, st, a);
+        } else {
+            hipLaunchKernelGGL(knz_alias_inv_header_kernel, dim3(gn), dim3(64), 0, st, a);
+            KNZ_LAUNCH_PROBED(knz_alias_inv_seg_kernel<false>, gseg, dim3(256), 0, st, a);
+            hipLaunchKernelGGL(knz_alias_inv_offsets_kernel, dim3(gn), dim3(64), 0, st, a);
+            KNZ_LAUNCH_PROBED(knz_alias_inv_seg_kernel<true>, gseg, dim3(256), 0, st, a);
+        }
+    }
+    return KNZ_OK;
+}
+
 static int run_stage(Handle* h, XfBatch& x, uint32_t t, bool forward, hipStream_t st) {
     const uint32_t nb = x.nblocks;
     const unsigned gseg = nb * x.spb;
@@ -939,6 +978,7 @@ static int run_stage(Handle* h, XfBatch& x, uint32_t t, bool forward, hipStream_
         return KNZ_OK;
     }
     if (t == KNZ_T_TEXT) return text_stage(h, x, forward, st);
+    if (t == KNZ_T_PACK || t == KNZ_T_DNA) return alias_stage(h, x, t == KNZ_T_DNA, forward, st);
     if (t == KNZ_T_BWT) return forward ? bwt_forward_stage(h, x, st) : bwt_inverse_stage(h, x, st);
     return knz_set_error(h, KNZ_ERR_INVALID_CODEC, "transform has no device implementation in this build");
 }

@@ -84,6 +84,28 @@ __global__ void knz_block_datatype_kernel(uint32_t nblocks, const uint64_t* blk_
     blk_dt[b] = (uint8_t)knz_magic_data_type(knz_magic_type((const uint8_t*)blk_off[b], blk_len[b]));
 }
 
+// internal/Global.go:346-419 DetectSimpleType over an order-0 histogram (the TEXT statistics and the PACK / DNA stage, alias.hip, share it)
+__device__ inline int knz_detect_simple_type(int n, const uint32_t* f0) {
+    if (n == 0) return KNZ_DT_UNDEFINED;
+    int sum = 0;
+    const char* dna = "acgntuACGNTU";
+    for (int i = 0; i < 12; i++) sum += (int)f0[(uint8_t)dna[i]];
+    if (sum > n - n / 12) return KNZ_DT_DNA;
+    const char* num = "0123456789+-*/=,.:; ";
+    sum = 0;
+    for (int i = 0; i < 20; i++) sum += (int)f0[(uint8_t)num[i]];
+    if (sum == n) return KNZ_DT_NUMERIC;
+    sum = (int)f0['+'] + (int)f0['/'];
+    for (int c = 'A'; c <= 'Z'; c++) sum += (int)f0[c] + (int)f0[c + 32];
+    for (int c = '0'; c <= '9'; c++) sum += (int)f0[c];
+    if (sum + (int)f0[0x3D] == n) return KNZ_DT_BASE64;
+    sum = 0;
+    for (int i = 0; i < 256; i++) sum += f0[i] > 0 ? 1 : 0;
+    if (sum == 256) return KNZ_DT_BIN;
+    if (sum <= 4) return KNZ_DT_SMALL_ALPHABET;
+    return KNZ_DT_UNDEFINED;
+}
+
 // ---- text statistics ------------------------------------------------------------------------------------------------------
 // The byte histogram and the rows / column of the pair histogram that the decision reads: row '&', row CR, column LF and the rows
 // of the UTF-8 lead bytes C2..F4. Row index of a previous byte in that table, -1 = not kept.
@@ -144,30 +166,7 @@ __global__ __launch_bounds__(256) void knz_text_stats_kernel(TextArgs a) {
         else notText = notText || (int)f0[32] < n / 50;
     }
     if (notText) {                                                       // detectTextType
-        int dt = KNZ_DT_UNDEFINED;
-        {   // DetectSimpleType
-            int sum = 0;
-            const char* dna = "acgntuACGNTU";
-            for (int i = 0; i < 12; i++) sum += (int)f0[(uint8_t)dna[i]];
-            if (sum > n - n / 12) dt = KNZ_DT_DNA;
-            if (dt == KNZ_DT_UNDEFINED) {
-                const char* num = "0123456789+-*/=,.:; ";
-                sum = 0;
-                for (int i = 0; i < 20; i++) sum += (int)f0[(uint8_t)num[i]];
-                if (sum == n) dt = KNZ_DT_NUMERIC;
-            }
-            if (dt == KNZ_DT_UNDEFINED) {
-                sum = (int)f0['+'] + (int)f0['/'];
-                for (int c = 'A'; c <= 'Z'; c++) sum += (int)f0[c] + (int)f0[c + 32];
-                for (int c = '0'; c <= '9'; c++) sum += (int)f0[c];
-                if (sum + (int)f0[0x3D] == n) dt = KNZ_DT_BASE64;
-            }
-            if (dt == KNZ_DT_UNDEFINED) {
-                sum = 0;
-                for (int i = 0; i < 256; i++) sum += f0[i] > 0 ? 1 : 0;
-                if (sum == 256) dt = KNZ_DT_BIN; else if (sum <= 4) dt = KNZ_DT_SMALL_ALPHABET;
-            }
-        }
+        int dt = knz_detect_simple_type(n, f0);
         if (dt == KNZ_DT_UNDEFINED) {                                    // every pair a legal UTF-8 start, enough continuation bytes => UTF8
             int sum = (int)f0[0xC0] + (int)f0[0xC1];
             for (int i = 0xF5; i < 256; i++) sum += (int)f0[i];
