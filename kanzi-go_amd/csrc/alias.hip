@@ -37,11 +37,7 @@ enum { KNZ_AL_MODE = 0, KNZ_AL_N0 = 1, KNZ_AL_HDR = 2, KNZ_AL_TOTAL = 3, KNZ_AL_
 // 4 digram (histogram and selection pending), 5 digram (header written, parse pending), 6 digram (offsets known, write pending)
 // modes (inverse): 0 failed / nothing to do, 1 fill, 2 / 3 packed, 4 digram (lengths pending), 5 digram (write pending)
 
-struct AliasArgs {
-    uint32_t nblocks, segs_per_block;
-    const uint64_t* in_ptr; const uint32_t* in_len;
-    const uint64_t* out_ptr; uint32_t out_cap;
-    uint32_t* out_len; int32_t* ok; const uint8_t* active;
+struct AliasArgs : XfIo {
     uint8_t* blk_dt;             // [nblocks] ctx["dataType"], may be null (= undefined, not recorded)
     uint32_t* state;             // [nblocks * KNZ_ALIAS_STATE_WORDS], zeroed by the host
     uint32_t* f1;                // [nblocks << 16] pair histogram, zeroed by the host (forward)

@@ -160,42 +160,6 @@ uint32_t knz_build_stream_header(const knz_cfg& cfg, int64_t inputSize, uint32_t
     return pos;
 }
 
-// ---- capability table ----------------------------------------------------------------------------------------------
-static bool transform_on_device(uint64_t t) {                    // packed sequence
-    for (int s = 42; s >= 0; s -= 6) {
-        const uint32_t id = (uint32_t)((t >> s) & 63);
-        if (!(id == KNZ_T_NONE || id == KNZ_T_BWT || id == KNZ_T_RANK || id == KNZ_T_MTFT || id == KNZ_T_ZRLT || id == KNZ_T_LZ || id == KNZ_T_LZX || id == KNZ_T_SRT || id == KNZ_T_LZP || id == KNZ_T_UTF || id == KNZ_T_TEXT || id == KNZ_T_PACK || id == KNZ_T_DNA)) return false;
-    }
-    return true;
-}
-static bool entropy_on_device(uint32_t e) { return e == KNZ_E_HUFFMAN || e == KNZ_E_NONE || e == KNZ_E_ANS0 || e == KNZ_E_ANS1 || e == KNZ_E_FPAQ; }
-
-extern "C" int knz_supports(uint64_t transform, uint32_t entropy) {
-    return (transform_on_device(transform) && entropy_on_device(entropy)) ? 1 : 0;
-}
-
-static uint32_t seq_len(uint64_t t) {
-    uint32_t n = 0;
-    for (int s = 42; s >= 0; s -= 6) if ((t >> s) & 63) n++;
-    return n ? n : 1;
-}
-
-extern "C" uint32_t knz_max_encoded_len(uint64_t transform, uint32_t n) {
-    // Sequence.go:189-205 over the hot-path transforms (BWT/SBRT: n+33, LZ/LZX/LZP: n+16 | n+n/64, SRT: n+1024)
-    uint64_t req = n;
-    for (int s = 42; s >= 0; s -= 6) {
-        uint32_t t = (uint32_t)((transform >> s) & 63);
-        uint64_t nxt = req;
-        if (t == KNZ_T_BWT || t == KNZ_T_RANK || t == KNZ_T_MTFT) nxt = req + 33;
-        else if (t == KNZ_T_LZ || t == KNZ_T_LZX || t == KNZ_T_LZP) nxt = req <= 1024 ? req + 16 : req + req / 64;
-        else if (t == KNZ_T_SRT) nxt = req + 4 * 256;
-        else if (t == KNZ_T_UTF) nxt = req + 8192;
-        else if (t == KNZ_T_PACK || t == KNZ_T_DNA) nxt = req + 1024;                       // AliasCodec.go:439
-        if (nxt > req) req = nxt;
-    }
-    return (uint32_t)std::min<uint64_t>(req, 0xFFFFFFFFu);
-}
-
 // ---- open / close --------------------------------------------------------------------------------------------------
 static thread_local std::string g_open_error;
 
@@ -367,6 +331,33 @@ extern "C" int knz_debug_prof(unsigned long long* out, int reset) {
 
 #include "knz_transforms.inc"
 
+// ---- capability tables: the transforms are the rows of kXfCodecs (knz_transforms.inc), the entropy codecs these -------------------
+struct EntropyCodec { uint32_t id, chunk, slot_stride, gather_y; };   // bytes per chunk, bytes per scratch slot of a chunk, y-dimension of the gather grid
+static const EntropyCodec kEntropyCodecs[] = {
+    {KNZ_E_NONE, KNZ_HUF_CHUNK, KNZ_CHUNK_STRIDE, 1},
+    {KNZ_E_HUFFMAN, KNZ_HUF_CHUNK, KNZ_CHUNK_STRIDE, 1},
+    {KNZ_E_FPAQ, KNZ_ANS1_CHUNK, KNZ_FPAQ_SLOT, 64},
+    {KNZ_E_ANS0, KNZ_HUF_CHUNK, KNZ_ANS_SLOT, 1},
+    {KNZ_E_ANS1, KNZ_ANS1_CHUNK, KNZ_ANS1_SLOT, 64},
+};
+static const EntropyCodec* entropy_codec(uint32_t e) {
+    for (const EntropyCodec& c : kEntropyCodecs) if (c.id == e) return &c;
+    return nullptr;
+}
+static bool entropy_on_device(uint32_t e) { return entropy_codec(e) != nullptr; }
+
+extern "C" int knz_supports(uint64_t transform, uint32_t entropy) {
+    for (int s = 42; s >= 0; s -= 6) if (!xf_codec((uint32_t)((transform >> s) & 63))) return 0;
+    return entropy_on_device(entropy) ? 1 : 0;
+}
+
+extern "C" uint32_t knz_max_encoded_len(uint64_t transform, uint32_t n) {     // Sequence.go:189-205
+    uint64_t req = n;
+    for (int s = 42; s >= 0; s -= 6)
+        if (const XfCodec* c = xf_codec((uint32_t)((transform >> s) & 63))) req += (c->grow_div && req > 1024) ? req / c->grow_div : c->grow;
+    return (uint32_t)std::min<uint64_t>(req, 0xFFFFFFFFu);
+}
+
 // ---- encode batch ----------------------------------------------------------------------------------------------------
 // d_src: nblocks blocks, block b at b*block_size (last one shorter). Output either the framed .knz body/stream
 // (framed=1) or per-block local streams at out_stride bytes (framed=0).
@@ -418,19 +409,16 @@ __global__ void knz_pack_results_kernel(uint32_t nblocks, const uint64_t* writte
 static int encode_batch(Handle* h, EncodeBatch& eb, hipStream_t st) {
     const knz_cfg& cfg = h->cfg;
     h->nprobes = 0;
-    if (!transform_on_device(cfg.transform) || !entropy_on_device(cfg.entropy))
+    if (!knz_supports(cfg.transform, cfg.entropy))
         return knz_set_error(h, KNZ_ERR_INVALID_CODEC, "transform/entropy combination has no device implementation in this build");
-    if (eb.n == 0) {
-        // Writer.Close on an empty stream: header + end marker only
-        eb.total_bits = 0;
-    }
+    const EntropyCodec& ec = *entropy_codec(cfg.entropy);
     const uint64_t bs = cfg.block_size;
-    const uint32_t nblocks = (uint32_t)((eb.n + bs - 1) / bs);
-    const uint32_t chunkSize = (cfg.entropy == KNZ_E_ANS1 || cfg.entropy == KNZ_E_FPAQ) ? KNZ_ANS1_CHUNK : KNZ_HUF_CHUNK;
+    const uint32_t nblocks = (uint32_t)((eb.n + bs - 1) / bs);       // (0: Writer.Close on an empty stream, header + end marker only)
+    const uint32_t chunkSize = ec.chunk;
     const uint32_t maxPost = knz_max_encoded_len(cfg.transform, (uint32_t)std::min<uint64_t>(bs, eb.n ? eb.n : 1));
     const uint32_t cpb = std::max<uint32_t>(1, (maxPost + chunkSize - 1) / chunkSize);
     const size_t nslots = (size_t)std::max<uint32_t>(nblocks, 1) * cpb;
-    const uint32_t slotStride = cfg.entropy == KNZ_E_ANS0 ? KNZ_ANS_SLOT : (cfg.entropy == KNZ_E_ANS1 ? KNZ_ANS1_SLOT : (cfg.entropy == KNZ_E_FPAQ ? KNZ_FPAQ_SLOT : KNZ_CHUNK_STRIDE));
+    const uint32_t slotStride = ec.slot_stride;
 
     if (h->blk_off.reserve(sizeof(uint64_t) * (nblocks + 1)) || h->blk_len.reserve(4 * (nblocks + 1)) ||
         h->blk_src_len.reserve(4 * (nblocks + 1)) || h->blk_skip.reserve(nblocks + 16) || h->blk_cksum.reserve(8 * (nblocks + 1)) ||
@@ -440,7 +428,6 @@ static int encode_batch(Handle* h, EncodeBatch& eb, hipStream_t st) {
         h->blk_dst_bit.reserve(8 * (nblocks + 1)) || h->total_bits.reserve(64) || h->blk_copy.reserve(nblocks + 16))
         return knz_set_error(h, KNZ_ERR_CREATE_COMPRESSOR, "device workspace allocation failed");
 
-    // block tables: absolute device addresses; blocks <= 15 bytes are copy blocks (CompressedStream.go:773-776)
     XfBatch xb;
     if (nblocks) {   // block tables, filled on the device: no staging copies, no host synchronisation in front of the first kernel
         const bool noneOnly = cfg.transform == 0;
@@ -472,11 +459,8 @@ static int encode_batch(Handle* h, EncodeBatch& eb, hipStream_t st) {
     if (nblocks && cfg.transform != 0) {
         xb.cur_ptr = h->blk_off.as<uint64_t>(); xb.cur_len = h->blk_len.as<uint32_t>(); xb.skip = h->blk_skip.as<uint8_t>();
         xb.blk_status = h->blk_status.as<int32_t>();
-        bool hasUtf = false;                                             // (or TEXT, PACK, DNA: the stages that read and write ctx["dataType"])
-        for (int sft = 42; sft >= 0; sft -= 6) {
-            const uint32_t id = (uint32_t)((cfg.transform >> sft) & 63);
-            hasUtf = hasUtf || id == KNZ_T_UTF || id == KNZ_T_TEXT || id == KNZ_T_PACK || id == KNZ_T_DNA;
-        }
+        bool hasUtf = false;                                             // (a stage that reads or writes ctx["dataType"])
+        for (int sft = 42; sft >= 0; sft -= 6) hasUtf = hasUtf || xf_codec((uint32_t)((cfg.transform >> sft) & 63))->data_type;
         if (hasUtf) {                                                    // ctx["dataType"] from the magic number of the untransformed block (:811-819)
             if (h->blk_dt.reserve(nblocks + 16)) return knz_set_error(h, KNZ_ERR_CREATE_COMPRESSOR, "device workspace allocation failed");
             hipLaunchKernelGGL(knz_block_datatype_kernel, dim3((nblocks + 63) / 64), dim3(64), 0, st, nblocks, (const uint64_t*)h->blk_off.as<uint64_t>(),
@@ -579,9 +563,10 @@ static int encode_batch(Handle* h, EncodeBatch& eb, hipStream_t st) {
         hipLaunchKernelGGL(knz_copy_units_kernel, dim3(nblocks * cpb), dim3(256), 0, st, ca);
     }
     LayoutArgs la;
+    uint32_t toks[8];
     la.nblocks = nblocks; la.chunks_per_block = cpb; la.unit_bits = h->unit_bits.as<uint32_t>();
     la.blk_len = h->blk_len.as<uint32_t>(); la.blk_src_len = h->blk_src_len.as<uint32_t>(); la.blk_skip = h->blk_skip.as<uint8_t>(); la.blk_copy = h->blk_copy.as<uint8_t>();
-    la.blk_cksum = h->blk_cksum.as<uint64_t>(); la.checksum_bits = cfg.checksum_bits; la.n_transforms = seq_len(cfg.transform);
+    la.blk_cksum = h->blk_cksum.as<uint64_t>(); la.checksum_bits = cfg.checksum_bits; la.n_transforms = (uint32_t)seq_tokens(cfg.transform, toks);
     la.chunk_size = chunkSize; la.payload_only = eb.payload_only; la.chunk_rel = h->chunk_rel.as<uint64_t>(); la.blk_written = h->blk_written.as<uint64_t>();
     la.blk_hdr = h->blk_hdr.as<uint32_t>();
     if (nblocks) hipLaunchKernelGGL(knz_layout_blocks_kernel, dim3(nblocks), dim3(256), 0, st, la);
@@ -612,7 +597,7 @@ static int encode_batch(Handle* h, EncodeBatch& eb, hipStream_t st) {
     ga.unit_src = h->unit_src.as<uint32_t>();
     ga.chunk_rel = h->chunk_rel.as<uint64_t>(); ga.blk_dst_bit = h->blk_dst_bit.as<uint64_t>(); ga.dst_words = (uint32_t*)eb.d_dst;
     ga.total_bits = h->total_bits.as<uint64_t>();
-    if (nblocks && !hufDirect) KNZ_LAUNCH_PROBED(knz_gather_kernel, dim3(nblocks * cpb, (cfg.entropy == KNZ_E_ANS1 || cfg.entropy == KNZ_E_FPAQ) ? 64 : 1), dim3(256), 0, st, ga);
+    if (nblocks && !hufDirect) KNZ_LAUNCH_PROBED(knz_gather_kernel, dim3(nblocks * cpb, ec.gather_y), dim3(256), 0, st, ga);
     hipEventRecord(h->ev[4], st);
     h->ev_valid = true;
 

@@ -45,7 +45,7 @@ struct PipeScope {
 
 static int decode_batch(Handle* h, DecodeBatch& db, hipStream_t st) {
     h->nprobes = 0;
-    if (!transform_on_device(db.transform) || !entropy_on_device(db.entropy))
+    if (!knz_supports(db.transform, db.entropy))
         return knz_set_error(h, KNZ_ERR_INVALID_CODEC, "transform/entropy combination has no device implementation in this build");
     uint32_t maxBlocks = db.nblocks;
     if (db.framed) {
@@ -74,7 +74,7 @@ static int decode_batch(Handle* h, DecodeBatch& db, hipStream_t st) {
     db.pre_len.assign(nblocks, 0); db.end_bit.assign(nblocks, 0); db.status.assign(nblocks, 0);
     if (nblocks == 0) return KNZ_OK;
     const uint32_t maxPre = db.payload_only ? db.given_len : knz_max_encoded_len(db.transform, db.block_size);
-    const uint32_t dchunk = (db.entropy == KNZ_E_ANS1 || db.entropy == KNZ_E_FPAQ) ? KNZ_ANS1_CHUNK : (uint32_t)KNZ_HUF_CHUNK;
+    const uint32_t dchunk = entropy_codec(db.entropy)->chunk;
     const uint32_t cpb = std::max<uint32_t>(1, (maxPre + dchunk - 1) / dchunk);
     const size_t nslots = (size_t)nblocks * cpb;
     if (h->blk_len.reserve(4 * (size_t)nblocks) || h->blk_skip.reserve(2 * (size_t)nblocks + 16) || h->blk_cksum.reserve(8 * (size_t)nblocks) ||
@@ -210,7 +210,7 @@ static int decode_batch(Handle* h, DecodeBatch& db, hipStream_t st) {
             pa.nblocks = nblocks; pa.chunks_per_block = cpb; pa.info = h->a1_info.as<uint32_t>(); pa.progress = h->pipe_prog.as<uint64_t>();
             pa.cur_ptr = h->blk_off.as<uint64_t>(); pa.cur_len = h->blk_len.as<uint32_t>(); pa.skip = h->blk_skip.as<uint8_t>() + nblocks; pa.side = xb.side;
             pa.blk_status = h->blk_status.as<int32_t>(); pa.piped = h->pipe_flag.as<uint8_t>();
-            pa.ranks_base = (uint64_t)h->xf_r3.p; pa.out_base = (uint64_t)h->xf_r2.p; pa.stride = xstride; pa.out_cap = (uint32_t)std::min<uint64_t>(xstride, 0xFFFFFFFFu);
+            pa.ranks_base = (uint64_t)h->xf_r3.p; pa.out_base = (uint64_t)h->xf_r2.p; pa.stride = xstride; pa.out_cap = xb.cap();
             pa.zrlt_stage = (uint32_t)(pnt - 1); pa.rank_stage = (uint32_t)(pnt - 2);
             pa.mode = 2;
             pa.group = pipeGroups ? h->pipe_group.as<uint8_t>() : (const uint8_t*)nullptr; pa.group_sel = 0;
@@ -627,7 +627,7 @@ extern "C" int knz_dev_assemble(void* handle, int64_t header_input_size, const v
 // ---- single kanzi.ByteTransform / EntropyEncoder / EntropyDecoder objects ------------------------------------------------
 // One ByteTransform object on one buffer: a batch of one block through the same stage kernels.
 static int transform_single(Handle* h, uint64_t type1, bool forward, const uint8_t* src, uint32_t n, uint8_t* dst, uint32_t cap, uint32_t* out_n) {
-    if (!transform1_on_device((uint32_t)type1)) return knz_set_error(h, KNZ_ERR_INVALID_CODEC, "transform has no device implementation in this build");
+    if (!xf_codec((uint32_t)type1)) return knz_set_error(h, KNZ_ERR_INVALID_CODEC, "transform has no device implementation in this build");
     *out_n = 0;
     if (n == 0 || cap == 0) return KNZ_OK;                                  // every Forward/Inverse returns (0,0,nil) on empty input
     if (type1 == KNZ_T_NONE) {
@@ -655,8 +655,6 @@ static int transform_single(Handle* h, uint64_t type1, bool forward, const uint8
     HIP_OK(hipMemcpyAsync(x.blk_status, &z32, 4, hipMemcpyHostToDevice, st));
     HIP_OK(hipStreamSynchronize(st));
     CommitArgs c = xf_commit_args(h, x, 0);
-    XfArgs probe = xf_args(h, x, 0);
-    (void)probe;
     hipLaunchKernelGGL(knz_xf_prepare_kernel, dim3(1), dim3(64), 0, st, c, x.out_ptr, x.ok);
     // the stage kernels take the capacity from the stride: make it the caller's dst length exactly
     x.stride = cap;

@@ -2,8 +2,6 @@
 // whole batch of blocks. Every stage runs for all blocks at once; a block whose stage declines (Forward error) keeps its
 // previous bytes and its skip bit (Sequence.go:86-91); applied blocks ping-pong between two device regions.
 
-static bool transform1_on_device(uint32_t t) { return t == KNZ_T_NONE || t == KNZ_T_BWT || t == KNZ_T_RANK || t == KNZ_T_MTFT || t == KNZ_T_ZRLT || t == KNZ_T_LZ || t == KNZ_T_LZX || t == KNZ_T_SRT || t == KNZ_T_LZP || t == KNZ_T_UTF || t == KNZ_T_TEXT || t == KNZ_T_PACK || t == KNZ_T_DNA; }
-
 static int seq_tokens(uint64_t t, uint32_t out[8]) {            // transform.New (Factory.go:58-95)
     int n = 0;
     for (int s = 42; s >= 0; s -= 6) { uint32_t id = (uint32_t)((t >> s) & 63); if (id) out[n++] = id; }
@@ -20,6 +18,18 @@ struct XfBatch {
     // the handle's configuration on the encode side, the stream header's values on the decode side; 0xFFFFFFFF = take the handle's
     uint32_t ctx_entropy = 0xFFFFFFFFu, ctx_block_size = 0;
     const uint8_t* piped = nullptr; int piped_zrlt = -1, piped_rank = -1;   // decode: blocks (and the two stages) the fused ZRLT / RANK inverse has already done (rank_pipe.hip)
+
+    uint32_t cap() const { return (uint32_t)std::min<uint64_t>(stride, 0xFFFFFFFFu); }   // bytes a stage may write per block
+    // the batch restricted to blocks g0 .. g0 + gn: every per-block table moves (workspaces indexed per group stay with the stage)
+    XfBatch group(uint32_t g0, uint32_t gn) const {
+        XfBatch g = *this;
+        auto adv = [g0](auto*& p) { if (p) p += g0; };
+        g.nblocks = gn; adv(g.cur_ptr); adv(g.cur_len); adv(g.skip); adv(g.side); adv(g.active); adv(g.take);
+        adv(g.out_ptr); adv(g.out_len); adv(g.ok); adv(g.blk_status); adv(g.blk_dt); adv(g.piped);
+        return g;
+    }
+    XfIo io() const { return XfIo{nblocks, spb, cur_ptr, cur_len, out_ptr, cap(), out_len, ok, active}; }
+    template <typename Args> Args args() const { Args a; static_cast<XfIo&>(a) = io(); return a; }   // a stage's argument struct, its block tables filled
 };
 
 static int xf_alloc(Handle* h, XfBatch& x, uint32_t nblocks, uint64_t stride) {
@@ -44,9 +54,7 @@ static CommitArgs xf_commit_args(Handle* h, const XfBatch& x, uint32_t stage) {
 }
 
 static XfArgs xf_args(Handle* h, const XfBatch& x, uint32_t mode) {
-    XfArgs a;
-    a.nblocks = x.nblocks; a.segs_per_block = x.spb; a.in_ptr = x.cur_ptr; a.in_len = x.cur_len; a.out_ptr = x.out_ptr;
-    a.out_cap = (uint32_t)std::min<uint64_t>(x.stride, 0xFFFFFFFFu); a.out_len = x.out_len; a.ok = x.ok; a.active = x.active;
+    XfArgs a = x.args<XfArgs>();
     a.seg_a = h->xf_sega.as<int32_t>(); a.seg_b = h->xf_segb.as<int32_t>(); a.mode = mode;
     return a;
 }
@@ -115,9 +123,8 @@ static bool ss_emu_check(const char* when, uint32_t total, uint32_t nb, const ui
 
 static unsigned knz_bits_for(uint64_t v) { unsigned b = 1; while ((1ull << b) <= v) b++; return b; }     // bits that hold the values 0..v
 
-static int bwt_forward_group(Handle* h, const XfBatch& xAll, hipStream_t st, uint32_t g0, uint32_t nb, const uint32_t* lenG, const uint8_t* takeG) {
-    XfBatch x = xAll;                                             // the group's slice of every per-block table
-    x.nblocks = nb; x.cur_ptr += g0; x.cur_len += g0; x.take += g0; x.out_ptr += g0; x.out_len += g0; x.ok += g0;
+static int bwt_forward_group(Handle* h, const XfBatch& x, hipStream_t st, const uint32_t* lenG, const uint8_t* takeG) {   // x: the group's slice of the batch
+    const uint32_t nb = x.nblocks;
     // geometry: blocks that do not take part get length 0 (gstart[b] == gstart[b+1], no radix tile)
     std::vector<uint32_t> geo(3 * (size_t)(nb + 1));
     uint32_t* gstart = geo.data(); uint32_t* tbase = gstart + (nb + 1); uint32_t* glen = tbase + (nb + 1);
@@ -291,44 +298,19 @@ static int bwt_forward_group(Handle* h, const XfBatch& xAll, hipStream_t st, uin
 #endif
         if (prof) fprintf(stderr, "suffix sort: h %llu -> %u in groups of 2..%u, %u in %u larger groups\n", (unsigned long long)hstep, mN, sgT, mL, nLg);
     }
-    BwtOutArgs oa; oa.g.nblocks = nb; oa.g.gstart = g.gstart; oa.g.in_ptr = x.cur_ptr; oa.g.in_len = g.in_len; oa.g.active = x.take;
-    oa.sa = sa; oa.rank = rank; oa.out_ptr = x.out_ptr; oa.out_cap = (uint32_t)std::min<uint64_t>(x.stride, 0xFFFFFFFFu);
-    oa.out_len = x.out_len; oa.ok = x.ok;
+    const XfIo io = x.io();
+    BwtOutArgs oa; oa.g.nblocks = io.nblocks; oa.g.gstart = g.gstart; oa.g.in_ptr = io.in_ptr; oa.g.in_len = g.in_len; oa.g.active = x.take;
+    oa.sa = sa; oa.rank = rank; oa.out_ptr = io.out_ptr; oa.out_cap = io.out_cap; oa.out_len = io.out_len; oa.ok = io.ok;
     KNZ_LAUNCH_PROBED(knz_bwt_output_kernel, dim3((total + 255) / 256), dim3(256), 0, st, oa, total);
     return KNZ_OK;
 }
 
-static int bwt_forward_stage(Handle* h, XfBatch& x, hipStream_t st) {
+static int bwt_inverse_group(Handle* h, const XfBatch& x, hipStream_t st) {   // x: the group's slice of the batch
     const uint32_t nb = x.nblocks;
-    hipLaunchKernelGGL(knz_bwt_precheck_kernel, dim3((nb + 63) / 64), dim3(64), 0, st, nb, x.cur_len, x.active,
-                       (uint32_t)std::min<uint64_t>(x.stride, 0xFFFFFFFFu), x.take, x.ok);
-    std::vector<uint32_t> len(nb);
-    std::vector<uint8_t> take(nb);
-    HIP_OK(hipMemcpyAsync(len.data(), x.cur_len, 4 * (size_t)nb, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(take.data(), x.take, nb, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    for (uint32_t g0 = 0; g0 < nb;) {
-        uint32_t gn = 0;
-        uint64_t tot = 0;
-        while (g0 + gn < nb && gn < KNZ_BWT_GROUP_BLOCKS) {
-            const uint64_t add = take[g0 + gn] ? len[g0 + gn] : 0;
-            if (gn > 0 && tot + add >= KNZ_BWT_GROUP_BYTES) break;
-            tot += add; gn++;
-        }
-        const int rc = bwt_forward_group(h, x, st, g0, gn, len.data() + g0, take.data() + g0);
-        if (rc) return rc;
-        g0 += gn;
-    }
-    return KNZ_OK;
-}
-
-static int bwt_inverse_group(Handle* h, const XfBatch& xAll, hipStream_t st, uint32_t g0, uint32_t nb) {
-    XfBatch x = xAll;
-    x.nblocks = nb; x.cur_ptr += g0; x.cur_len += g0; x.active += g0; x.out_ptr += g0; x.out_len += g0; x.ok += g0;
+    const XfIo io = x.io();
     BwtInvArgs a;
-    a.nblocks = nb; a.gstart = h->xf_gstart.as<uint32_t>(); a.in_ptr = x.cur_ptr; a.in_len = x.cur_len; a.active = x.active;
-    a.hdr = (uint32_t*)((uint8_t*)h->xf_misc.p + 16 * (size_t)(nb + 1)); a.out_ptr = x.out_ptr;
-    a.out_cap = (uint32_t)std::min<uint64_t>(x.stride, 0xFFFFFFFFu); a.out_len = x.out_len; a.ok = x.ok;
+    a.nblocks = io.nblocks; a.gstart = h->xf_gstart.as<uint32_t>(); a.in_ptr = io.in_ptr; a.in_len = io.in_len; a.active = io.active;
+    a.hdr = (uint32_t*)((uint8_t*)h->xf_misc.p + 16 * (size_t)(nb + 1)); a.out_ptr = io.out_ptr; a.out_cap = io.out_cap; a.out_len = io.out_len; a.ok = io.ok;
     uint32_t* d_plen = (uint32_t*)h->xf_misc.p;
     hipLaunchKernelGGL(knz_bwt_inv_header_kernel, dim3((nb + 63) / 64), dim3(64), 0, st, a, d_plen);
     std::vector<uint32_t> plen(nb), gstart(nb + 1);
@@ -395,19 +377,24 @@ static int bwt_inverse_group(Handle* h, const XfBatch& xAll, hipStream_t st, uin
     return KNZ_OK;
 }
 
-static int bwt_inverse_stage(Handle* h, XfBatch& x, hipStream_t st) {
+// Both directions take the batch in groups of consecutive blocks, by input length (inverse: header included, an upper bound of the payload)
+static int bwt_stage(Handle* h, XfBatch& x, uint32_t, bool forward, hipStream_t st) {
     const uint32_t nb = x.nblocks;
     std::vector<uint32_t> len(nb);
+    std::vector<uint8_t> take(nb, 1);
+    if (forward) hipLaunchKernelGGL(knz_bwt_precheck_kernel, dim3((nb + 63) / 64), dim3(64), 0, st, nb, x.cur_len, x.active, x.cap(), x.take, x.ok);
     HIP_OK(hipMemcpyAsync(len.data(), x.cur_len, 4 * (size_t)nb, hipMemcpyDeviceToHost, st));
+    if (forward) HIP_OK(hipMemcpyAsync(take.data(), x.take, nb, hipMemcpyDeviceToHost, st));   // (the inverse takes every block of the batch)
     HIP_OK(hipStreamSynchronize(st));
-    for (uint32_t g0 = 0; g0 < nb;) {                               // groups by input length (header included: an upper bound of the payload)
+    for (uint32_t g0 = 0; g0 < nb;) {
         uint32_t gn = 0;
         uint64_t tot = 0;
-        while (g0 + gn < nb && gn < (1u << 20)) {
-            if (gn > 0 && tot + len[g0 + gn] >= KNZ_BWT_GROUP_BYTES) break;
-            tot += len[g0 + gn]; gn++;
+        while (g0 + gn < nb && gn < KNZ_BWT_GROUP_BLOCKS) {
+            const uint64_t add = take[g0 + gn] ? len[g0 + gn] : 0;
+            if (gn > 0 && tot + add >= KNZ_BWT_GROUP_BYTES) break;
+            tot += add; gn++;
         }
-        const int rc = bwt_inverse_group(h, x, st, g0, gn);
+        const int rc = forward ? bwt_forward_group(h, x.group(g0, gn), st, len.data() + g0, take.data() + g0) : bwt_inverse_group(h, x.group(g0, gn), st);
         if (rc) return rc;
         g0 += gn;
     }
@@ -455,7 +442,7 @@ static void text_params(uint32_t entropy, uint32_t block_size, uint32_t& kind, u
     logHash = lg;
 }
 
-static int text_stage(Handle* h, XfBatch& x, bool forward, hipStream_t st) {
+static int text_stage(Handle* h, XfBatch& x, uint32_t, bool forward, hipStream_t st) {
     const uint32_t nb = x.nblocks;
     uint32_t kind, logHash;
     // the stream's own ctx values, not the handle's: a stream is decoded with what ITS header says (the reference builds the codec from the
@@ -476,9 +463,9 @@ static int text_stage(Handle* h, XfBatch& x, bool forward, hipStream_t st) {
         return knz_set_error(h, KNZ_ERR_CREATE_COMPRESSOR, "device workspace allocation failed (TEXT)");
     for (uint32_t g0 = 0; g0 < nb; g0 += G) {
         const uint32_t gn = std::min<uint32_t>(G, nb - g0);
-        TextArgs a;
-        a.nblocks = gn; a.in_ptr = x.cur_ptr + g0; a.in_len = x.cur_len + g0; a.out_ptr = x.out_ptr + g0; a.out_cap = (uint32_t)std::min<uint64_t>(x.stride, 0xFFFFFFFFu);
-        a.out_len = x.out_len + g0; a.ok = x.ok + g0; a.active = x.active + g0; a.blk_dt = x.blk_dt ? x.blk_dt + g0 : nullptr;
+        const XfBatch g = x.group(g0, gn);
+        TextArgs a = g.args<TextArgs>();
+        a.blk_dt = g.blk_dt;
         a.tmode = h->text_mode.as<int32_t>() + g0; a.dict_map = h->text_map.as<int32_t>(); a.ent = h->text_ent.as<uint32_t>();
         a.stat = h->text_stat.as<uint32_t>(); a.log_hash = logHash; a.kind = kind; a.chain_count = h->text_cnt.as<uint32_t>();
         TextParArgs pa;
@@ -498,35 +485,23 @@ static int text_stage(Handle* h, XfBatch& x, bool forward, hipStream_t st) {
         }
         // the chain kernels take the blocks the parallel ones left (no fixed point within their rounds, a dictionary that wraps) and the
         // KNZ_TEXT_CHAIN runs
-        if (forward) {
-            hipLaunchKernelGGL(knz_text_stats_kernel, dim3(gn), dim3(256), 0, st, a);
-            if (par) KNZ_LAUNCH_PROBED(knz_text_forward_par_kernel, dim3(gn), dim3(KNZ_TCP_THREADS), 0, st, pa);
-            if (par && pa.prof) {
-                std::vector<unsigned long long> pr((size_t)gn * 8);
-                HIP_OK(hipStreamSynchronize(st));
-                HIP_OK(hipMemcpy(pr.data(), pa.prof, pr.size() * 8, hipMemcpyDeviceToHost));
-                for (uint32_t q = 0; q < gn; q++) {
-                    const unsigned long long* r = pr.data() + (size_t)q * 8;
-                    if (r[4]) fprintf(stderr, "TEXT block %u: tokens %llu rounds %llu cycles A %llu B %llu C %llu D %llu\n", g0 + q, r[7], r[6], r[1] - r[0], r[2] - r[1], r[3] - r[2], r[4] - r[3]);
-                }
+        if (forward) hipLaunchKernelGGL(knz_text_stats_kernel, dim3(gn), dim3(256), 0, st, a);
+        else HIP_OK(hipMemsetAsync(a.tmode, 0, (size_t)gn * 4, st));
+        if (par && forward) KNZ_LAUNCH_PROBED(knz_text_forward_par_kernel, dim3(gn), dim3(KNZ_TCP_THREADS), 0, st, pa);
+        if (par && !forward) KNZ_LAUNCH_PROBED(knz_text_inverse_par_kernel, dim3(gn), dim3(KNZ_TCP_THREADS), 0, st, pa);
+        if (par && pa.prof) {
+            std::vector<unsigned long long> pr((size_t)gn * 8);
+            HIP_OK(hipStreamSynchronize(st));
+            HIP_OK(hipMemcpy(pr.data(), pa.prof, pr.size() * 8, hipMemcpyDeviceToHost));
+            for (uint32_t q = 0; q < gn; q++) {
+                const unsigned long long* r = pr.data() + (size_t)q * 8;
+                if (r[4] && forward) fprintf(stderr, "TEXT block %u: tokens %llu rounds %llu cycles A %llu B %llu C %llu D %llu\n", g0 + q, r[7], r[6], r[1] - r[0], r[2] - r[1], r[3] - r[2], r[4] - r[3]);
+                if (r[4] && !forward) fprintf(stderr, "TEXT inverse block %u: tokens %llu cycles I %llu II %llu III %llu IV %llu\n", g0 + q, r[7], r[1] - r[0], r[2] - r[1], r[3] - r[2], r[4] - r[3]);
             }
-            HIP_OK(hipMemsetAsync(h->text_map.p, 0xFF, ((size_t)gn << logHash) * 4, st));
-            KNZ_LAUNCH_PROBED(knz_text_forward_chain_kernel, dim3(gn), dim3(64), 0, st, a);
-        } else {
-            HIP_OK(hipMemsetAsync(a.tmode, 0, (size_t)gn * 4, st));
-            if (par) KNZ_LAUNCH_PROBED(knz_text_inverse_par_kernel, dim3(gn), dim3(KNZ_TCP_THREADS), 0, st, pa);
-            if (par && pa.prof) {
-                std::vector<unsigned long long> pr((size_t)gn * 8);
-                HIP_OK(hipStreamSynchronize(st));
-                HIP_OK(hipMemcpy(pr.data(), pa.prof, pr.size() * 8, hipMemcpyDeviceToHost));
-                for (uint32_t q = 0; q < gn; q++) {
-                    const unsigned long long* r = pr.data() + (size_t)q * 8;
-                    if (r[4]) fprintf(stderr, "TEXT inverse block %u: tokens %llu cycles I %llu II %llu III %llu IV %llu\n", g0 + q, r[7], r[1] - r[0], r[2] - r[1], r[3] - r[2], r[4] - r[3]);
-                }
-            }
-            HIP_OK(hipMemsetAsync(h->text_map.p, 0xFF, ((size_t)gn << logHash) * 4, st));
-            KNZ_LAUNCH_PROBED(knz_text_inverse_chain_kernel, dim3(gn), dim3(64), 0, st, a);
         }
+        HIP_OK(hipMemsetAsync(h->text_map.p, 0xFF, ((size_t)gn << logHash) * 4, st));
+        if (forward) KNZ_LAUNCH_PROBED(knz_text_forward_chain_kernel, dim3(gn), dim3(64), 0, st, a);
+        else KNZ_LAUNCH_PROBED(knz_text_inverse_chain_kernel, dim3(gn), dim3(64), 0, st, a);
     }
     return KNZ_OK;
 }
@@ -791,20 +766,19 @@ static int lz_inverse_par(Handle* h, XfBatch& x, const LzArgs& la, hipStream_t s
 // ---- PACK / DNA (alias.hip) -------------------------------------------------------------------------------------------------
 // Bounded groups of blocks like the UTF stage: the forward stage keeps a 65536-bin pair histogram per block (256 KiB), so the workspace is
 // sized to a group of at most 64 blocks (16 MiB), not to the batch.
-static int alias_stage(Handle* h, XfBatch& x, bool onlyDna, bool forward, hipStream_t st) {
+static int alias_stage(Handle* h, XfBatch& x, uint32_t t, bool forward, hipStream_t st) {
     const uint32_t nb = x.nblocks;
     const uint32_t G = std::min<uint32_t>(nb, 64u);
     if (h->alias_state.reserve((size_t)G * KNZ_ALIAS_STATE_WORDS * 4) || (forward && h->alias_f1.reserve(((size_t)G << 16) * 4)))
         return knz_set_error(h, forward ? KNZ_ERR_CREATE_COMPRESSOR : KNZ_ERR_CREATE_DECOMPRESSOR, "device workspace allocation failed (PACK)");
-    const uint32_t cap = (uint32_t)std::min<uint64_t>(x.stride, 0xFFFFFFFFu);
     for (uint32_t g0 = 0; g0 < nb; g0 += G) {
         const uint32_t gn = std::min<uint32_t>(G, nb - g0);
-        AliasArgs a;
-        a.nblocks = gn; a.segs_per_block = x.spb; a.in_ptr = x.cur_ptr + g0; a.in_len = x.cur_len + g0; a.out_ptr = x.out_ptr + g0; a.out_cap = cap;
-        a.out_len = x.out_len + g0; a.ok = x.ok + g0; a.active = x.active + g0; a.blk_dt = (forward && x.blk_dt) ? x.blk_dt + g0 : nullptr;
+        const XfBatch g = x.group(g0, gn);
+        AliasArgs a = g.args<AliasArgs>();
+        a.blk_dt = forward ? g.blk_dt : nullptr;
         a.state = h->alias_state.as<uint32_t>(); a.f1 = h->alias_f1.as<uint32_t>(); a.seg = h->xf_sega.as<uint32_t>() + (size_t)g0 * x.spb * 4;
-        a.only_dna = onlyDna ? 1u : 0u;
-        a.h1_chunks = (uint32_t)std::max<uint64_t>(1, ((uint64_t)cap + KNZ_ALIAS_H1_CHUNK - 1) / KNZ_ALIAS_H1_CHUNK);
+        a.only_dna = t == KNZ_T_DNA ? 1u : 0u;
+        a.h1_chunks = (uint32_t)std::max<uint64_t>(1, ((uint64_t)a.out_cap + KNZ_ALIAS_H1_CHUNK - 1) / KNZ_ALIAS_H1_CHUNK);
         HIP_OK(hipMemsetAsync(h->alias_state.p, 0, (size_t)gn * KNZ_ALIAS_STATE_WORDS * 4, st));
         const dim3 gseg(x.spb, gn);
         if (forward) {
@@ -827,163 +801,192 @@ static int alias_stage(Handle* h, XfBatch& x, bool onlyDna, bool forward, hipStr
     return KNZ_OK;
 }
 
-static int run_stage(Handle* h, XfBatch& x, uint32_t t, bool forward, hipStream_t st) {
-    const uint32_t nb = x.nblocks;
-    const unsigned gseg = nb * x.spb;
-    if (t == KNZ_T_NONE) return KNZ_OK;
-    if (t == KNZ_T_RANK || t == KNZ_T_MTFT) {
-        XfArgs a = xf_args(h, x, t == KNZ_T_RANK ? 2 : 1);
-        if (forward) {
-            hipLaunchKernelGGL(knz_sbrt_seg_last2_kernel, dim3(gseg), dim3(64), 0, st, a);
-            hipLaunchKernelGGL(knz_sbrt_carry_kernel, dim3(nb), dim3(256), 0, st, a);
-            if (t == KNZ_T_RANK) KNZ_LAUNCH_PROBED(knz_sbrt_apply_kernel<2>, dim3(gseg), dim3(64), 0, st, a);
-            else hipLaunchKernelGGL(knz_sbrt_apply_kernel<1>, dim3(gseg), dim3(64), 0, st, a);
-        } else {
-            if (t == KNZ_T_RANK) {
-                const char* v = knz_test_switch("KNZ_RANK_VARIANT");                                         // (tests: 0 = the round-1 kernel as a cross-check; -DKNZ_MEASURE builds: the earlier forms)
-                const int vi = v ? atoi(v) : 5;
-                if (knz_test_switch("KNZ_RANK_UNPACKED") != nullptr) a.mode |= 0x100;                   // (tests: the form for blocks > 8 MiB on small inputs)
-                if (const char* cv = knz_test_switch("KNZ_RANK_CUT")) a.mode |= ((uint32_t)atoi(cv) / 64u) << 12;   // (tests: where the packed form hands over to the three-register form, ranks)
-                if (vi == 0) KNZ_LAUNCH_PROBED(knz_sbrt_inverse_kernel<2>, dim3(nb), dim3(64), 0, st, a);   // the round-1 form (tests: cross-check of the chain kernel)
+// ---- the stages whose kernels need no host code of their own: RANK / MTFT, ZRLT, LZ / LZX, SRT, LZP, UTF ------------------------
+static int sbrt_stage(Handle* h, XfBatch& x, uint32_t t, bool forward, hipStream_t st) {
+    const uint32_t nb = x.nblocks, gseg = nb * x.spb;
+    XfArgs a = xf_args(h, x, t == KNZ_T_RANK ? 2 : 1);
+    if (forward) {
+        hipLaunchKernelGGL(knz_sbrt_seg_last2_kernel, dim3(gseg), dim3(64), 0, st, a);
+        hipLaunchKernelGGL(knz_sbrt_carry_kernel, dim3(nb), dim3(256), 0, st, a);
+        if (t == KNZ_T_RANK) KNZ_LAUNCH_PROBED(knz_sbrt_apply_kernel<2>, dim3(gseg), dim3(64), 0, st, a);
+        else hipLaunchKernelGGL(knz_sbrt_apply_kernel<1>, dim3(gseg), dim3(64), 0, st, a);
+    } else {
+        if (t == KNZ_T_RANK) {
+            const char* v = knz_test_switch("KNZ_RANK_VARIANT");                                         // (tests: 0 = the round-1 kernel as a cross-check; -DKNZ_MEASURE builds: the earlier forms)
+            const int vi = v ? atoi(v) : 5;
+            if (knz_test_switch("KNZ_RANK_UNPACKED") != nullptr) a.mode |= 0x100;                   // (tests: the form for blocks > 8 MiB on small inputs)
+            if (const char* cv = knz_test_switch("KNZ_RANK_CUT")) a.mode |= ((uint32_t)atoi(cv) / 64u) << 12;   // (tests: where the packed form hands over to the three-register form, ranks)
+            if (vi == 0) KNZ_LAUNCH_PROBED(knz_sbrt_inverse_kernel<2>, dim3(nb), dim3(64), 0, st, a);   // the round-1 form (tests: cross-check of the chain kernel)
 #ifdef KNZ_MEASURE                                                                             // earlier and measurement forms of the step (docs/HISTORY.md "Tried and dropped")
-                else if (vi == 3) KNZ_LAUNCH_PROBED((knz_rank_inverse_chain_kernel<2, 2>), dim3(nb), dim3(64), 0, st, a);   // round-2 first form (SALU arithmetic)
-                else if (vi == 4) KNZ_LAUNCH_PROBED((knz_rank_inverse_chain_kernel<2, 4>), dim3(nb), dim3(64), 0, st, a);   // round-2 second form: lane-1 copies of (q, e) kept in registers
-                else if (vi == 6) KNZ_LAUNCH_PROBED((knz_rank_inverse_chain_kernel<2, 12 | 64>), dim3(nb), dim3(64), 0, st, a);   // (measured, slower) words with ranks >= 64 as straight-line bodies over 2 / 4 registers
-                else if (vi == 7) KNZ_LAUNCH_PROBED((knz_rank_inverse_chain_kernel<2, 4 | 16>), dim3(nb), dim3(64), 0, st, a);   // (measurement: 4 instructions beside the chain in every low step)
-                else if (vi == 8) KNZ_LAUNCH_PROBED((knz_rank_inverse_chain_kernel<2, 4 | 32>), dim3(nb), dim3(64), 0, st, a);   // (measurement: 4 instructions on the chain in every low step)
+            else if (vi == 3) KNZ_LAUNCH_PROBED((knz_rank_inverse_chain_kernel<2, 2>), dim3(nb), dim3(64), 0, st, a);   // round-2 first form (SALU arithmetic)
+            else if (vi == 4) KNZ_LAUNCH_PROBED((knz_rank_inverse_chain_kernel<2, 4>), dim3(nb), dim3(64), 0, st, a);   // round-2 second form: lane-1 copies of (q, e) kept in registers
+            else if (vi == 6) KNZ_LAUNCH_PROBED((knz_rank_inverse_chain_kernel<2, 12 | 64>), dim3(nb), dim3(64), 0, st, a);   // (measured, slower) words with ranks >= 64 as straight-line bodies over 2 / 4 registers
+            else if (vi == 7) KNZ_LAUNCH_PROBED((knz_rank_inverse_chain_kernel<2, 4 | 16>), dim3(nb), dim3(64), 0, st, a);   // (measurement: 4 instructions beside the chain in every low step)
+            else if (vi == 8) KNZ_LAUNCH_PROBED((knz_rank_inverse_chain_kernel<2, 4 | 32>), dim3(nb), dim3(64), 0, st, a);   // (measurement: 4 instructions on the chain in every low step)
 #endif
-                else KNZ_LAUNCH_PROBED((knz_rank_inverse_chain_kernel<2, 4 | 64>), dim3(nb), dim3(64), 0, st, a);           // default: the lane-1 copies are DPP operands of the step's own instructions
+            else KNZ_LAUNCH_PROBED((knz_rank_inverse_chain_kernel<2, 4 | 64>), dim3(nb), dim3(64), 0, st, a);           // default: the lane-1 copies are DPP operands of the step's own instructions
 #if !defined(KNZ_HIP_EMU)
-                if (vi != 0 && vi != 3 && knz_measure_switch("KNZ_RANK_PROF") != nullptr) {                  // diagnostics: time of every block's chain
-                    std::vector<unsigned long long> tk(std::min<size_t>(nb, 1024));
-                    if (hipStreamSynchronize(st) == hipSuccess && hipMemcpyFromSymbol(tk.data(), HIP_SYMBOL(g_knz_rank_ticks), tk.size() * 8) == hipSuccess) {
-                        fprintf(stderr, "inverse RANK chain, ms per block:");
-                        for (size_t q = 0; q < tk.size(); q++) fprintf(stderr, " %.0f", (double)tk[q] / 1e5);
-                        fprintf(stderr, "\n");
-                    }
+            if (vi != 0 && vi != 3 && knz_measure_switch("KNZ_RANK_PROF") != nullptr) {                  // diagnostics: time of every block's chain
+                std::vector<unsigned long long> tk(std::min<size_t>(nb, 1024));
+                if (hipStreamSynchronize(st) == hipSuccess && hipMemcpyFromSymbol(tk.data(), HIP_SYMBOL(g_knz_rank_ticks), tk.size() * 8) == hipSuccess) {
+                    fprintf(stderr, "inverse RANK chain, ms per block:");
+                    for (size_t q = 0; q < tk.size(); q++) fprintf(stderr, " %.0f", (double)tk[q] / 1e5);
+                    fprintf(stderr, "\n");
                 }
+            }
 #endif
-            }
-            else if (knz_test_switch("KNZ_MTFT_CHAIN") != nullptr) KNZ_LAUNCH_PROBED(knz_sbrt_inverse_kernel<1>, dim3(nb), dim3(64), 0, st, a);   // (tests: the one-wave form)
-            else {   // move-to-front permutes positions independently of the content: per-segment permutations, composed per block
-                hipLaunchKernelGGL(knz_mtft_inv_perm_kernel, dim3(gseg), dim3(64), 0, st, a);
-                hipLaunchKernelGGL(knz_mtft_inv_compose_kernel, dim3(nb), dim3(256), 0, st, a);
-                hipLaunchKernelGGL(knz_mtft_inv_apply_kernel, dim3(gseg), dim3(64), 0, st, a);
-            }
         }
-        return KNZ_OK;
-    }
-    if (t == KNZ_T_ZRLT) {
-        XfArgs a = xf_args(h, x, 0);
-        if (forward) {
-            hipLaunchKernelGGL(knz_zrlt_seg_lastnz_kernel, dim3(gseg), dim3(256), 0, st, a);
-            hipLaunchKernelGGL(knz_zrlt_carry_kernel, dim3(nb), dim3(64), 0, st, a);
-            hipLaunchKernelGGL(knz_zrlt_seg_kernel<false>, dim3(gseg), dim3(256), 0, st, a);
-            hipLaunchKernelGGL(knz_zrlt_offsets_kernel, dim3(nb), dim3(64), 0, st, a);
-            hipLaunchKernelGGL(knz_zrlt_seg_kernel<true>, dim3(gseg), dim3(256), 0, st, a);
-        } else {
-            hipLaunchKernelGGL(knz_zrlti_seg_lastnd_kernel, dim3(gseg), dim3(256), 0, st, a);
-            hipLaunchKernelGGL(knz_zrlt_carry_kernel, dim3(nb), dim3(64), 0, st, a);
-            hipLaunchKernelGGL(knz_zrlti_seg_kernel<false>, dim3(gseg), dim3(256), 0, st, a);
-            hipLaunchKernelGGL(knz_zrlti_offsets_kernel, dim3(nb), dim3(64), 0, st, a);
-            hipLaunchKernelGGL(knz_zrlti_zero_kernel, dim3(64, nb), dim3(256), 0, st, a);
-            hipLaunchKernelGGL(knz_zrlti_seg_kernel<true>, dim3(gseg), dim3(256), 0, st, a);
+        else if (knz_test_switch("KNZ_MTFT_CHAIN") != nullptr) KNZ_LAUNCH_PROBED(knz_sbrt_inverse_kernel<1>, dim3(nb), dim3(64), 0, st, a);   // (tests: the one-wave form)
+        else {   // move-to-front permutes positions independently of the content: per-segment permutations, composed per block
+            hipLaunchKernelGGL(knz_mtft_inv_perm_kernel, dim3(gseg), dim3(64), 0, st, a);
+            hipLaunchKernelGGL(knz_mtft_inv_compose_kernel, dim3(nb), dim3(256), 0, st, a);
+            hipLaunchKernelGGL(knz_mtft_inv_apply_kernel, dim3(gseg), dim3(64), 0, st, a);
         }
-        return KNZ_OK;
     }
-    if (t == KNZ_T_LZ || t == KNZ_T_LZX) {
-        const unsigned hashLog = t == KNZ_T_LZX ? 19 : 16;
-        const uint64_t bstride = ((x.stride + 1024 + 63) & ~(uint64_t)63);
-        if (forward && (h->lz_hash.reserve(((size_t)nb << hashLog) * 4) || h->lz_tk.reserve(bstride * nb) || h->lz_mb.reserve(bstride * nb) || h->lz_ml.reserve(bstride * nb)))
-            return knz_set_error(h, KNZ_ERR_CREATE_COMPRESSOR, "device workspace allocation failed (LZ)");
-        LzArgs a;
-        a.nblocks = nb; a.in_ptr = x.cur_ptr; a.in_len = x.cur_len; a.out_ptr = x.out_ptr; a.out_cap = (uint32_t)std::min<uint64_t>(x.stride, 0xFFFFFFFFu);
-        a.out_len = x.out_len; a.ok = x.ok; a.active = x.active; a.hashes = h->lz_hash.as<int32_t>(); a.tk = h->lz_tk.as<uint8_t>();
-        a.mb = h->lz_mb.as<uint8_t>(); a.ml = h->lz_ml.as<uint8_t>(); a.buf_stride = bstride; a.extra = t == KNZ_T_LZX ? 1 : 0; a.blk_dt = forward ? x.blk_dt : nullptr;
-        if (forward && knz_test_switch("KNZ_LZ_CHAIN") == nullptr) {
-            const int rc = lz_forward_par(h, x, a, hashLog, st);
-            if (rc == 0) return KNZ_OK;
-            if (rc != 1) return knz_set_error(h, KNZ_ERR_UNKNOWN, "LZ forward: HIP error in the table-free forms");   // (1 = does not fit: first form below)
-        }
-        if (forward) {                                                               // first form: the parse keeps its own hash table (KNZ_LZ_CHAIN, or a batch beyond one sort)
-            HIP_OK(hipMemsetAsync(h->lz_hash.p, 0, ((size_t)nb << hashLog) * 4, st));        // hash tables start empty (:265-271)
-            KNZ_LAUNCH_PROBED(knz_lz_forward_kernel, dim3(nb), dim3(64), 0, st, a);
-        } else {
-            // parallel form first; the one-wave kernel takes the blocks it leaves (damaged or unusual streams)
-            const int rc = lz_inverse_par(h, x, a, st);
-            if (rc) return rc;
-            a.active = h->lzi_serial.as<uint8_t>();
-            KNZ_LAUNCH_PROBED(knz_lz_inverse_kernel, dim3(nb), dim3(64), 0, st, a);
-        }
-        return KNZ_OK;
-    }
-    if (t == KNZ_T_SRT) {
-        XfArgs a = xf_args(h, x, 0);
-        if (!forward) { KNZ_LAUNCH_PROBED(knz_srt_inverse_kernel, dim3(nb), dim3(64), 0, st, a); return KNZ_OK; }
-        if (knz_test_switch("KNZ_SRT_CHAIN") != nullptr) { hipLaunchKernelGGL(knz_srt_forward_kernel, dim3(nb), dim3(64), 0, st, a); return KNZ_OK; }   // (tests: the one-wave form)
-        // forward = MTFT ranks (segment-parallel) + first occurrences + a stable partition by symbol (srt_lzp.hip)
-        const uint64_t tstride = (x.stride + 63) & ~(uint64_t)63;
-        if (h->srt_tab.reserve((size_t)nb * KNZ_SRT_TAB * 4 + 64) || h->srt_tmp.reserve((size_t)nb * tstride + 64) || h->srt_ptrs.reserve((size_t)nb * 24 + 64))
-            return knz_set_error(h, KNZ_ERR_CREATE_COMPRESSOR, "device workspace allocation failed (SRT)");
-        uint64_t* ptrs = h->srt_ptrs.as<uint64_t>();
-        uint32_t* dummyLen = (uint32_t*)(ptrs + nb);
-        int32_t* dummyOk = (int32_t*)(ptrs + 2 * (size_t)nb);
-        hipLaunchKernelGGL(knz_fill_ptrs_kernel, dim3((nb + 63) / 64), dim3(64), 0, st, nb, (uint64_t)h->srt_tmp.p, tstride, ptrs);
-        SrtParArgs pa;
-        pa.nblocks = nb; pa.segs_per_block = x.spb; pa.in_ptr = x.cur_ptr; pa.in_len = x.cur_len; pa.out_ptr = x.out_ptr; pa.out_cap = a.out_cap;
-        pa.out_len = x.out_len; pa.ok = x.ok; pa.active = x.active; pa.tab = h->srt_tab.as<uint32_t>(); pa.rank_ptr = ptrs; pa.seg_cnt = h->xf_sega.as<int32_t>();
-        hipLaunchKernelGGL(knz_srt_stats_kernel, dim3(nb), dim3(256), 0, st, pa);
-        XfArgs m = xf_args(h, x, 1);                                  // MTFT ranks of every position into the scratch blocks
-        m.out_ptr = ptrs; m.out_cap = 0xFFFFFFFFu; m.out_len = dummyLen; m.ok = dummyOk;
-        hipLaunchKernelGGL(knz_sbrt_seg_last2_kernel, dim3(gseg), dim3(64), 0, st, m);
-        hipLaunchKernelGGL(knz_sbrt_carry_kernel, dim3(nb), dim3(256), 0, st, m);
-        hipLaunchKernelGGL(knz_sbrt_apply_kernel<1>, dim3(gseg), dim3(64), 0, st, m);
-        hipLaunchKernelGGL(knz_srt_seg_count_kernel, dim3(gseg), dim3(64), 0, st, pa);
-        hipLaunchKernelGGL(knz_srt_seg_scan_kernel, dim3(nb), dim3(256), 0, st, pa);
-        hipLaunchKernelGGL(knz_srt_scatter_kernel, dim3(gseg), dim3(64), 0, st, pa);
-        return KNZ_OK;
-    }
-    if (t == KNZ_T_LZP) {
-        if (h->lz_hash.reserve(((size_t)nb << 16) * 4)) return knz_set_error(h, KNZ_ERR_CREATE_COMPRESSOR, "device workspace allocation failed (LZP)");
-        LzArgs a;
-        a.nblocks = nb; a.in_ptr = x.cur_ptr; a.in_len = x.cur_len; a.out_ptr = x.out_ptr; a.out_cap = (uint32_t)std::min<uint64_t>(x.stride, 0xFFFFFFFFu);
-        a.out_len = x.out_len; a.ok = x.ok; a.active = x.active; a.hashes = h->lz_hash.as<int32_t>(); a.tk = nullptr; a.mb = nullptr; a.ml = nullptr;
-        a.buf_stride = 0; a.extra = 0; a.blk_dt = nullptr;
-        HIP_OK(hipMemsetAsync(h->lz_hash.p, 0, ((size_t)nb << 16) * 4, st));                   // both directions start from an empty table (:1001-1005, :1100-1104)
-        if (forward) KNZ_LAUNCH_PROBED(knz_lzp_forward_kernel, dim3(nb), dim3(64), 0, st, a);
-        else KNZ_LAUNCH_PROBED(knz_lzp_inverse_kernel, dim3(nb), dim3(64), 0, st, a);
-        return KNZ_OK;
-    }
-    if (t == KNZ_T_UTF) {
-        // bounded groups of blocks (like the suffix sort): the forward stage keeps a 2^22-entry alias map per block (16 MiB), so the
-        // workspace is sized to a group of at most 64 blocks (1 GiB), not to the batch: a stream of 15 000 64-KiB blocks still fits
-        const uint32_t G = std::min<uint32_t>(nb, 64u);
-        const uint64_t bitsStride = ((x.stride >> 3) + 64) & ~(uint64_t)15;
-        if (forward ? (h->utf_map.reserve(((size_t)G << 22) * 4) || h->utf_syms.reserve((size_t)G * 32768 * 4) || h->utf_ranks.reserve((size_t)G * 32768 * 4) ||
-                       h->utf_bits.reserve((size_t)G * bitsStride + 64))
-                    : h->utf_inv.reserve((size_t)G * 32768 * 8))
-            return knz_set_error(h, KNZ_ERR_CREATE_COMPRESSOR, "device workspace allocation failed (UTF)");
-        for (uint32_t g0 = 0; g0 < nb; g0 += G) {
-            const uint32_t gn = std::min<uint32_t>(G, nb - g0);
-            UtfArgs a;
-            a.nblocks = gn; a.in_ptr = x.cur_ptr + g0; a.in_len = x.cur_len + g0; a.out_ptr = x.out_ptr + g0; a.out_cap = (uint32_t)std::min<uint64_t>(x.stride, 0xFFFFFFFFu);
-            a.out_len = x.out_len + g0; a.ok = x.ok + g0; a.active = x.active + g0; a.alias_map = h->utf_map.as<int32_t>(); a.symlist = h->utf_syms.as<uint32_t>();
-            a.ranks = h->utf_ranks.as<uint32_t>(); a.inv_map = h->utf_inv.as<uint64_t>(); a.chain_bits = h->utf_bits.as<uint8_t>(); a.bits_stride = bitsStride;
-            a.blk_dt = x.blk_dt ? x.blk_dt + g0 : nullptr;
-            if (forward) {
-                HIP_OK(hipMemsetAsync(h->utf_map.p, 0, ((size_t)gn << 22) * 4, st));
-                KNZ_LAUNCH_PROBED(knz_utf_forward_kernel, dim3(gn), dim3(KNZ_UTF_FWD_THREADS), 0, st, a);
-            } else KNZ_LAUNCH_PROBED(knz_utf_inverse_kernel, dim3(gn), dim3(64), 0, st, a);
-        }
-        return KNZ_OK;
-    }
-    if (t == KNZ_T_TEXT) return text_stage(h, x, forward, st);
-    if (t == KNZ_T_PACK || t == KNZ_T_DNA) return alias_stage(h, x, t == KNZ_T_DNA, forward, st);
-    if (t == KNZ_T_BWT) return forward ? bwt_forward_stage(h, x, st) : bwt_inverse_stage(h, x, st);
-    return knz_set_error(h, KNZ_ERR_INVALID_CODEC, "transform has no device implementation in this build");
+    return KNZ_OK;
 }
 
-// Forward sequence. On entry x.cur_ptr/cur_len describe the source blocks, skip[] = 0xFF for active blocks.
+static int zrlt_stage(Handle* h, XfBatch& x, uint32_t, bool forward, hipStream_t st) {
+    const uint32_t nb = x.nblocks, gseg = nb * x.spb;
+    XfArgs a = xf_args(h, x, 0);
+    if (forward) {
+        hipLaunchKernelGGL(knz_zrlt_seg_lastnz_kernel, dim3(gseg), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(knz_zrlt_carry_kernel, dim3(nb), dim3(64), 0, st, a);
+        hipLaunchKernelGGL(knz_zrlt_seg_kernel<false>, dim3(gseg), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(knz_zrlt_offsets_kernel, dim3(nb), dim3(64), 0, st, a);
+        hipLaunchKernelGGL(knz_zrlt_seg_kernel<true>, dim3(gseg), dim3(256), 0, st, a);
+    } else {
+        hipLaunchKernelGGL(knz_zrlti_seg_lastnd_kernel, dim3(gseg), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(knz_zrlt_carry_kernel, dim3(nb), dim3(64), 0, st, a);
+        hipLaunchKernelGGL(knz_zrlti_seg_kernel<false>, dim3(gseg), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(knz_zrlti_offsets_kernel, dim3(nb), dim3(64), 0, st, a);
+        hipLaunchKernelGGL(knz_zrlti_zero_kernel, dim3(64, nb), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(knz_zrlti_seg_kernel<true>, dim3(gseg), dim3(256), 0, st, a);
+    }
+    return KNZ_OK;
+}
+
+static int lz_stage(Handle* h, XfBatch& x, uint32_t t, bool forward, hipStream_t st) {
+    const uint32_t nb = x.nblocks;
+    const unsigned hashLog = t == KNZ_T_LZX ? 19 : 16;
+    const uint64_t bstride = ((x.stride + 1024 + 63) & ~(uint64_t)63);
+    if (forward && (h->lz_hash.reserve(((size_t)nb << hashLog) * 4) || h->lz_tk.reserve(bstride * nb) || h->lz_mb.reserve(bstride * nb) || h->lz_ml.reserve(bstride * nb)))
+        return knz_set_error(h, KNZ_ERR_CREATE_COMPRESSOR, "device workspace allocation failed (LZ)");
+    LzArgs a = x.args<LzArgs>();
+    a.hashes = h->lz_hash.as<int32_t>(); a.tk = h->lz_tk.as<uint8_t>(); a.mb = h->lz_mb.as<uint8_t>(); a.ml = h->lz_ml.as<uint8_t>(); a.buf_stride = bstride; a.extra = t == KNZ_T_LZX ? 1 : 0; a.blk_dt = forward ? x.blk_dt : nullptr;
+    if (forward && knz_test_switch("KNZ_LZ_CHAIN") == nullptr) {
+        const int rc = lz_forward_par(h, x, a, hashLog, st);
+        if (rc == 0) return KNZ_OK;
+        if (rc != 1) return knz_set_error(h, KNZ_ERR_UNKNOWN, "LZ forward: HIP error in the table-free forms");   // (1 = does not fit: first form below)
+    }
+    if (forward) {                                                               // first form: the parse keeps its own hash table (KNZ_LZ_CHAIN, or a batch beyond one sort)
+        HIP_OK(hipMemsetAsync(h->lz_hash.p, 0, ((size_t)nb << hashLog) * 4, st));        // hash tables start empty (:265-271)
+        KNZ_LAUNCH_PROBED(knz_lz_forward_kernel, dim3(nb), dim3(64), 0, st, a);
+    } else {
+        // parallel form first; the one-wave kernel takes the blocks it leaves (damaged or unusual streams)
+        const int rc = lz_inverse_par(h, x, a, st);
+        if (rc) return rc;
+        a.active = h->lzi_serial.as<uint8_t>();
+        KNZ_LAUNCH_PROBED(knz_lz_inverse_kernel, dim3(nb), dim3(64), 0, st, a);
+    }
+    return KNZ_OK;
+}
+
+static int srt_stage(Handle* h, XfBatch& x, uint32_t, bool forward, hipStream_t st) {
+    const uint32_t nb = x.nblocks, gseg = nb * x.spb;
+    XfArgs a = xf_args(h, x, 0);
+    if (!forward) { KNZ_LAUNCH_PROBED(knz_srt_inverse_kernel, dim3(nb), dim3(64), 0, st, a); return KNZ_OK; }
+    if (knz_test_switch("KNZ_SRT_CHAIN") != nullptr) { hipLaunchKernelGGL(knz_srt_forward_kernel, dim3(nb), dim3(64), 0, st, a); return KNZ_OK; }   // (tests: the one-wave form)
+    // forward = MTFT ranks (segment-parallel) + first occurrences + a stable partition by symbol (srt_lzp.hip)
+    const uint64_t tstride = (x.stride + 63) & ~(uint64_t)63;
+    if (h->srt_tab.reserve((size_t)nb * KNZ_SRT_TAB * 4 + 64) || h->srt_tmp.reserve((size_t)nb * tstride + 64) || h->srt_ptrs.reserve((size_t)nb * 24 + 64))
+        return knz_set_error(h, KNZ_ERR_CREATE_COMPRESSOR, "device workspace allocation failed (SRT)");
+    uint64_t* ptrs = h->srt_ptrs.as<uint64_t>();
+    uint32_t* dummyLen = (uint32_t*)(ptrs + nb);
+    int32_t* dummyOk = (int32_t*)(ptrs + 2 * (size_t)nb);
+    hipLaunchKernelGGL(knz_fill_ptrs_kernel, dim3((nb + 63) / 64), dim3(64), 0, st, nb, (uint64_t)h->srt_tmp.p, tstride, ptrs);
+    SrtParArgs pa = x.args<SrtParArgs>();
+    pa.tab = h->srt_tab.as<uint32_t>(); pa.rank_ptr = ptrs; pa.seg_cnt = h->xf_sega.as<int32_t>();
+    hipLaunchKernelGGL(knz_srt_stats_kernel, dim3(nb), dim3(256), 0, st, pa);
+    XfArgs m = xf_args(h, x, 1);                                  // MTFT ranks of every position into the scratch blocks
+    m.out_ptr = ptrs; m.out_cap = 0xFFFFFFFFu; m.out_len = dummyLen; m.ok = dummyOk;
+    hipLaunchKernelGGL(knz_sbrt_seg_last2_kernel, dim3(gseg), dim3(64), 0, st, m);
+    hipLaunchKernelGGL(knz_sbrt_carry_kernel, dim3(nb), dim3(256), 0, st, m);
+    hipLaunchKernelGGL(knz_sbrt_apply_kernel<1>, dim3(gseg), dim3(64), 0, st, m);
+    hipLaunchKernelGGL(knz_srt_seg_count_kernel, dim3(gseg), dim3(64), 0, st, pa);
+    hipLaunchKernelGGL(knz_srt_seg_scan_kernel, dim3(nb), dim3(256), 0, st, pa);
+    hipLaunchKernelGGL(knz_srt_scatter_kernel, dim3(gseg), dim3(64), 0, st, pa);
+    return KNZ_OK;
+}
+
+static int lzp_stage(Handle* h, XfBatch& x, uint32_t, bool forward, hipStream_t st) {
+    const uint32_t nb = x.nblocks;
+    if (h->lz_hash.reserve(((size_t)nb << 16) * 4)) return knz_set_error(h, KNZ_ERR_CREATE_COMPRESSOR, "device workspace allocation failed (LZP)");
+    LzArgs a = x.args<LzArgs>();
+    a.hashes = h->lz_hash.as<int32_t>(); a.tk = nullptr; a.mb = nullptr; a.ml = nullptr; a.buf_stride = 0; a.extra = 0; a.blk_dt = nullptr;
+    HIP_OK(hipMemsetAsync(h->lz_hash.p, 0, ((size_t)nb << 16) * 4, st));                   // both directions start from an empty table (:1001-1005, :1100-1104)
+    if (forward) KNZ_LAUNCH_PROBED(knz_lzp_forward_kernel, dim3(nb), dim3(64), 0, st, a);
+    else KNZ_LAUNCH_PROBED(knz_lzp_inverse_kernel, dim3(nb), dim3(64), 0, st, a);
+    return KNZ_OK;
+}
+
+static int utf_stage(Handle* h, XfBatch& x, uint32_t, bool forward, hipStream_t st) {
+    const uint32_t nb = x.nblocks;
+    // bounded groups of blocks (like the suffix sort): the forward stage keeps a 2^22-entry alias map per block (16 MiB), so the
+    // workspace is sized to a group of at most 64 blocks (1 GiB), not to the batch: a stream of 15 000 64-KiB blocks still fits
+    const uint32_t G = std::min<uint32_t>(nb, 64u);
+    const uint64_t bitsStride = ((x.stride >> 3) + 64) & ~(uint64_t)15;
+    if (forward ? (h->utf_map.reserve(((size_t)G << 22) * 4) || h->utf_syms.reserve((size_t)G * 32768 * 4) || h->utf_ranks.reserve((size_t)G * 32768 * 4) ||
+                   h->utf_bits.reserve((size_t)G * bitsStride + 64))
+                : h->utf_inv.reserve((size_t)G * 32768 * 8))
+        return knz_set_error(h, KNZ_ERR_CREATE_COMPRESSOR, "device workspace allocation failed (UTF)");
+    for (uint32_t g0 = 0; g0 < nb; g0 += G) {
+        const uint32_t gn = std::min<uint32_t>(G, nb - g0);
+        const XfBatch g = x.group(g0, gn);
+        UtfArgs a = g.args<UtfArgs>();
+        a.alias_map = h->utf_map.as<int32_t>(); a.symlist = h->utf_syms.as<uint32_t>(); a.ranks = h->utf_ranks.as<uint32_t>();
+        a.inv_map = h->utf_inv.as<uint64_t>(); a.chain_bits = h->utf_bits.as<uint8_t>(); a.bits_stride = bitsStride; a.blk_dt = g.blk_dt;
+        if (forward) {
+            HIP_OK(hipMemsetAsync(h->utf_map.p, 0, ((size_t)gn << 22) * 4, st));
+            KNZ_LAUNCH_PROBED(knz_utf_forward_kernel, dim3(gn), dim3(KNZ_UTF_FWD_THREADS), 0, st, a);
+        } else KNZ_LAUNCH_PROBED(knz_utf_inverse_kernel, dim3(gn), dim3(64), 0, st, a);
+    }
+    return KNZ_OK;
+}
+
+// ---- the transforms of this build: THE list of ids. knz_supports, knz_max_encoded_len, the ctx["dataType"] decision of encode_batch and run_stage read it ----
+struct XfCodec {
+    uint32_t id; const char* name;
+    uint32_t grow, grow_div;        // MaxEncodedLen(n) = n + grow, or n + n / grow_div where grow_div != 0 and n > 1024 (Sequence.go:189-205 over each transform's own rule)
+    bool data_type;                 // the stage reads or writes ctx["dataType"]
+    int (*stage)(Handle*, XfBatch&, uint32_t id, bool forward, hipStream_t);   // null: NullTransform, nothing to run
+};
+static const XfCodec kXfCodecs[] = {
+    {KNZ_T_NONE, "NONE", 0, 0, false, nullptr},
+    {KNZ_T_BWT, "BWT", 33, 0, false, bwt_stage},
+    {KNZ_T_LZ, "LZ", 16, 64, false, lz_stage},
+    {KNZ_T_ZRLT, "ZRLT", 0, 0, false, zrlt_stage},
+    {KNZ_T_MTFT, "MTFT", 33, 0, false, sbrt_stage},
+    {KNZ_T_RANK, "RANK", 33, 0, false, sbrt_stage},
+    {KNZ_T_TEXT, "TEXT", 0, 0, true, text_stage},
+    {KNZ_T_SRT, "SRT", 4 * 256, 0, false, srt_stage},
+    {KNZ_T_LZP, "LZP", 16, 64, false, lzp_stage},
+    {KNZ_T_LZX, "LZX", 16, 64, false, lz_stage},
+    {KNZ_T_UTF, "UTF", 8192, 0, true, utf_stage},
+    {KNZ_T_PACK, "PACK", 1024, 0, true, alias_stage},      // AliasCodec.go:439
+    {KNZ_T_DNA, "DNA", 1024, 0, true, alias_stage},
+};
+static const XfCodec* xf_codec(uint32_t id) {
+    for (const XfCodec& c : kXfCodecs) if (c.id == id) return &c;
+    return nullptr;
+}
+
+static int run_stage(Handle* h, XfBatch& x, uint32_t t, bool forward, hipStream_t st) {
+    const XfCodec* c = xf_codec(t);
+    if (!c) return knz_set_error(h, KNZ_ERR_INVALID_CODEC, "transform has no device implementation in this build");
+    return c->stage ? c->stage(h, x, t, forward, st) : KNZ_OK;
+}
+
 // bytes that enter a stage, summed over the live blocks (diagnostics: bench.py prices every kernel on the bytes its stage really saw)
 __global__ __launch_bounds__(256) void knz_xf_sum_len_kernel(uint32_t nblocks, const uint32_t* len, const uint8_t* active, unsigned long long* out) {
     __shared__ unsigned long long s_part[256];
@@ -994,13 +997,13 @@ __global__ __launch_bounds__(256) void knz_xf_sum_len_kernel(uint32_t nblocks, c
     if (threadIdx.x == 0) { unsigned long long t = 0; for (int i = 0; i < 256; i++) t += s_part[i]; *out = t; }
 }
 
+// Forward sequence. On entry x.cur_ptr/cur_len describe the source blocks, skip[] = 0xFF for active blocks.
 static int forward_sequence(Handle* h, XfBatch& x, uint64_t transformType, hipStream_t st) {
     uint32_t toks[8];
     const int nt = seq_tokens(transformType, toks);
     if (h->stage_sum.reserve(8 * 8)) return knz_set_error(h, KNZ_ERR_CREATE_COMPRESSOR, "device workspace allocation failed");
     HIP_OK(hipMemsetAsync(h->stage_sum.p, 0, 64, st));
     for (int i = 0; i < nt; i++) {
-        if (!transform1_on_device(toks[i])) return knz_set_error(h, KNZ_ERR_INVALID_CODEC, "transform has no device implementation in this build");
         CommitArgs c = xf_commit_args(h, x, (uint32_t)i);
         const unsigned gb = (x.nblocks + 63) / 64;
         hipLaunchKernelGGL(knz_xf_sum_len_kernel, dim3(1), dim3(256), 0, st, x.nblocks, (const uint32_t*)x.cur_len, (const uint8_t*)x.active, h->stage_sum.as<unsigned long long>() + i);
@@ -1023,7 +1026,6 @@ static int inverse_sequence(Handle* h, XfBatch& x, uint64_t transformType, hipSt
     const int nt = seq_tokens(transformType, toks);
     const unsigned gb = (x.nblocks + 63) / 64;
     for (int i = nt - 1; i >= 0; i--) {
-        if (!transform1_on_device(toks[i])) return knz_set_error(h, KNZ_ERR_INVALID_CODEC, "transform has no device implementation in this build");
         if (toks[i] == KNZ_T_NONE) continue;
         CommitArgs c = xf_commit_args(h, x, (uint32_t)i);
         // active = block is live and its skip bit for this stage is clear

@@ -28,11 +28,7 @@
 #define KNZ_LZ_MAX_MATCH (65535 + 254 + 4)
 #define KNZ_LZ_MIN_BLOCK 24
 
-struct LzArgs {
-    uint32_t nblocks;
-    const uint64_t* in_ptr; const uint32_t* in_len;
-    const uint64_t* out_ptr; uint32_t out_cap;
-    uint32_t* out_len; int32_t* ok; const uint8_t* active;
+struct LzArgs : XfIo {
     int32_t* hashes;            // [nblocks << hashLog]
     uint8_t* tk; uint8_t* mb; uint8_t* ml;     // [nblocks * buf_stride] each
     uint64_t buf_stride;

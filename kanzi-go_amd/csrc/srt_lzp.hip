@@ -171,10 +171,7 @@ __global__ __launch_bounds__(64) void knz_srt_forward_kernel(XfArgs a) {
 // occurrence of the k-th new symbol replaced by k, and every byte that is not a run head has MTFT rank 0 anyway. What is left is
 // SRT's layout: a stable partition of the positions by symbol (bucket of c = its ranks in order), done per 8 KiB segment with
 // per-segment symbol counts, a scan over the segments and a match-any inside each row of 64 positions.
-struct SrtParArgs {
-    uint32_t nblocks, segs_per_block;
-    const uint64_t* in_ptr; const uint32_t* in_len; const uint64_t* out_ptr; uint32_t out_cap;
-    uint32_t* out_len; int32_t* ok; const uint8_t* active;
+struct SrtParArgs : XfIo {
     uint32_t* tab;                 // [nblocks * KNZ_SRT_TAB]: start[256], firstPos[256], firstRank[256], hs
     const uint64_t* rank_ptr;      // [nblocks] MTFT ranks of every position (knz_sbrt_apply_kernel<1>)
     int32_t* seg_cnt;              // [nblocks * segs_per_block * 256]

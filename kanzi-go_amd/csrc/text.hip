@@ -21,11 +21,7 @@
 enum { KNZ_DT_UNDEFINED = 0, KNZ_DT_TEXT = 1, KNZ_DT_MULTIMEDIA = 2, KNZ_DT_EXE = 3, KNZ_DT_NUMERIC = 4, KNZ_DT_BASE64 = 5, KNZ_DT_DNA = 6,
        KNZ_DT_BIN = 7, KNZ_DT_UTF8 = 8, KNZ_DT_SMALL_ALPHABET = 9 };     // internal/Global.go:26-40
 
-struct TextArgs {
-    uint32_t nblocks;
-    const uint64_t* in_ptr; const uint32_t* in_len;
-    const uint64_t* out_ptr; uint32_t out_cap;
-    uint32_t* out_len; int32_t* ok; const uint8_t* active;
+struct TextArgs : XfIo {
     uint8_t* blk_dt;               // [nblocks] ctx["dataType"] (reference numbering); may be null (= undefined, not recorded)
     int32_t* tmode;                // [nblocks] forward: the block's mode byte, -1 = the stage declines
     int32_t* dict_map;             // [nblocks << log_hash] slot -> entry index, 0xFF-filled by the host

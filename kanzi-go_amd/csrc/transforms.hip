@@ -14,7 +14,8 @@
 
 #define KNZ_SEG 8192
 
-struct XfArgs {
+// The block tables of a stage: the head of every stage kernel's argument struct (the host fills it in one place, XfBatch::io)
+struct XfIo {
     uint32_t nblocks;
     uint32_t segs_per_block;
     const uint64_t* in_ptr;       // [nblocks] device address of the block's current bytes
@@ -24,6 +25,9 @@ struct XfArgs {
     uint32_t* out_len;            // [nblocks]
     int32_t* ok;                  // [nblocks] 1 applied, 0 declined (transform skipped), <0: -(kanzi error)
     const uint8_t* active;        // [nblocks] 0 = block does not run this stage (copy block / earlier failure)
+};
+
+struct XfArgs : XfIo {
     int32_t* seg_a;               // per-segment scratch (meaning depends on the transform)
     int32_t* seg_b;
     uint32_t mode;                // SBRT mode: 1 MTF, 2 RANK, 3 TIMESTAMP

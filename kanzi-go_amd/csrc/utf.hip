@@ -22,11 +22,7 @@
 #define KNZ_UTF_MAX_SYMS 32768
 #define KNZ_UTF_MAP_LOG 22
 
-struct UtfArgs {
-    uint32_t nblocks;
-    const uint64_t* in_ptr; const uint32_t* in_len;
-    const uint64_t* out_ptr; uint32_t out_cap;
-    uint32_t* out_len; int32_t* ok; const uint8_t* active;
+struct UtfArgs : XfIo {
     int32_t* alias_map;          // [nblocks << 22], zeroed by the host (forward)
     uint32_t* symlist;           // [nblocks * 32768] distinct code points in order of first touch (forward)
     uint32_t* ranks;             // [nblocks * 32768] sort position of symlist[j] (forward)

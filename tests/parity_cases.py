@@ -326,6 +326,39 @@ def check_short_inner_block(be):
         c.close()
 
 
+def check_codec_table(be):
+    """The library's one table of transforms and its table of entropy codecs, seen through the C ABI: the support set (== the Python names of
+    api._TNAMES), what the single-object call answers for every id, and MaxEncodedLen's growth per id (Sequence.go:189-205)."""
+    import ctypes as C
+    L = K.load_library(be.lib)
+    supported = {0, 1, 3, 6, 7, 8, 10, 13, 14, 16, 17, 18, 19}
+    assert set(K.api._TNAMES.values()) == supported
+    for tid in range(64):
+        assert L.knz_supports(tid << 42, 0) == (1 if tid in supported else 0), tid
+    eight_bwt = sum(1 << (42 - 6 * slot) for slot in range(8))
+    assert L.knz_supports(eight_bwt, 0) == 1
+    for slot in range(8):                                   # one unsupported id (2) in any slot of a sequence
+        assert L.knz_supports(eight_bwt + (1 << (42 - 6 * slot)), 0) == 0, slot
+    for e in range(32):
+        assert L.knz_supports(0, e) == (1 if e in (0, 1, 2, 5, 8) else 0), e
+    c = K.Codec("NONE", "NONE", 1 << 16, lib=be.lib)
+    src, out, n = (C.c_uint8 * 64)(*range(64)), (C.c_uint8 * 4096)(), C.c_uint32()
+    for tid in range(64):
+        rc = L.knz_transform_forward(c.h, tid, src, 64, out, 4096, C.byref(n))
+        assert (rc == 3) == (tid not in supported), (tid, rc)                # KNZ_ERR_INVALID_CODEC
+        assert tid not in supported or rc in (0, -1), (tid, rc)             # KNZ_OK / KNZ_SKIP
+    c.close()
+    growth = {1: lambda n: 33, 7: lambda n: 33, 8: lambda n: 33, 13: lambda n: 1024, 17: lambda n: 8192, 18: lambda n: 1024, 19: lambda n: 1024,
+              0: lambda n: 0, 6: lambda n: 0, 10: lambda n: 0}
+    for tid in (3, 14, 16):
+        growth[tid] = lambda n: 16 if n <= 1024 else n // 64
+    assert set(growth) == supported
+    for tid, g in growth.items():
+        for n in (1, 1024, 1025, 5000, 1 << 20):
+            assert L.knz_max_encoded_len(tid << 42, n) == n + g(n), (tid, n)
+    assert L.knz_max_encoded_len(K.transform_type("BWT+RANK+ZRLT"), 5000) == 5066
+
+
 def transform_inputs(zrlt=False, max_len=1 << 30):
     for name, data in _transform_inputs(zrlt):
         if len(data) <= max_len:

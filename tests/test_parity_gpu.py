@@ -309,6 +309,10 @@ def test_short_block_inside_stream(be):
     P.check_short_inner_block(be)
 
 
+def test_codec_table(be):
+    P.check_codec_table(be)
+
+
 def test_bwt_inverse_list_ranking(be, monkeypatch):
     P.check_bwt_list_ranking(be, monkeypatch)
     monkeypatch.setenv("KNZ_BWT_RANK_MIN", "256")
