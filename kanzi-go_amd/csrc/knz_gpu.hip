@@ -270,6 +270,16 @@ extern "C" int knz_last_kernel_times(void* handle, char* names, int names_cap, f
     return n;
 }
 
+// the first n flag bytes of a workspace buffer, brought over: their sum, or with only != 0 the number of them that have this value
+static int sum_flags(const DevBuf& buf, size_t n, uint8_t only, uint64_t* value) {
+    *value = 0;
+    if (n == 0) return KNZ_OK;
+    std::vector<uint8_t> f(n);
+    if (hipMemcpy(f.data(), buf.p, f.size(), hipMemcpyDeviceToHost) != hipSuccess) return KNZ_ERR_UNKNOWN;
+    for (uint8_t v : f) *value += only ? (v == only ? 1 : 0) : v;
+    return KNZ_OK;
+}
+
 extern "C" int knz_last_counter(void* handle, int id, uint64_t* value) {
     Handle* h = (Handle*)handle;
     if (!h || !value || id < KNZ_COUNTER_HUF_SERIAL_CHUNKS || id > KNZ_COUNTER_STAGE_BYTES0 + 7 || (id > KNZ_COUNTER_RANK_PIPE_BLOCKS && id < KNZ_COUNTER_STAGE_BYTES0)) return KNZ_ERR_INVALID_PARAM;
@@ -285,40 +295,10 @@ extern "C" int knz_last_counter(void* handle, int id, uint64_t* value) {
         return KNZ_OK;
     }
     if (id == KNZ_COUNTER_LZ_FWD_ROUNDS) { *value = h->lzs_rounds; return KNZ_OK; }
-    if (id == KNZ_COUNTER_RANK_PIPE_BLOCKS) {
-        if (h->pipe_n == 0) return KNZ_OK;
-        std::vector<uint8_t> f(h->pipe_n);
-        if (hipMemcpy(f.data(), h->pipe_flag.p, f.size(), hipMemcpyDeviceToHost) != hipSuccess) return KNZ_ERR_UNKNOWN;
-        uint64_t n = 0;
-        for (uint8_t v : f) n += v;
-        *value = n;
-        return KNZ_OK;
-    }
-    if (id == KNZ_COUNTER_LZ_FWD_SERIAL_BLOCKS) {
-        if (h->lzs_n == 0) return KNZ_OK;
-        std::vector<uint8_t> f(h->lzs_n);
-        if (hipMemcpy(f.data(), h->lzs_misc.p, f.size(), hipMemcpyDeviceToHost) != hipSuccess) return KNZ_ERR_UNKNOWN;
-        uint64_t n = 0;
-        for (uint8_t v : f) n += v == 2 ? 1 : 0;
-        *value = n;
-        return KNZ_OK;
-    }
-    if (id == KNZ_COUNTER_LZ_INV_SERIAL_BLOCKS) {
-        if (h->lzi_serial_n == 0) return KNZ_OK;
-        std::vector<uint8_t> f(h->lzi_serial_n);
-        if (hipMemcpy(f.data(), h->lzi_serial.p, f.size(), hipMemcpyDeviceToHost) != hipSuccess) return KNZ_ERR_UNKNOWN;
-        uint64_t n = 0;
-        for (uint8_t v : f) n += v;
-        *value = n;
-        return KNZ_OK;
-    }
-    if (h->huf_fallback_n == 0) return KNZ_OK;
-    std::vector<uint8_t> f(h->huf_fallback_n);
-    if (hipMemcpy(f.data(), h->huf_fallback.p, f.size(), hipMemcpyDeviceToHost) != hipSuccess) return KNZ_ERR_UNKNOWN;
-    uint64_t n = 0;
-    for (uint8_t v : f) n += v;
-    *value = n;
-    return KNZ_OK;
+    if (id == KNZ_COUNTER_RANK_PIPE_BLOCKS) return sum_flags(h->pipe_flag, h->pipe_n, 0, value);
+    if (id == KNZ_COUNTER_LZ_FWD_SERIAL_BLOCKS) return sum_flags(h->lzs_misc, h->lzs_n, 2, value);
+    if (id == KNZ_COUNTER_LZ_INV_SERIAL_BLOCKS) return sum_flags(h->lzi_serial, h->lzi_serial_n, 0, value);
+    return sum_flags(h->huf_fallback, h->huf_fallback_n, 0, value);
 }
 
 #ifdef KNZ_PROFILE_PHASES
@@ -330,22 +310,9 @@ extern "C" int knz_debug_prof(unsigned long long* out, int reset) {
 #endif
 
 #include "knz_transforms.inc"
+#include "knz_batch.inc"
 
-// ---- capability tables: the transforms are the rows of kXfCodecs (knz_transforms.inc), the entropy codecs these -------------------
-struct EntropyCodec { uint32_t id, chunk, slot_stride, gather_y; };   // bytes per chunk, bytes per scratch slot of a chunk, y-dimension of the gather grid
-static const EntropyCodec kEntropyCodecs[] = {
-    {KNZ_E_NONE, KNZ_HUF_CHUNK, KNZ_CHUNK_STRIDE, 1},
-    {KNZ_E_HUFFMAN, KNZ_HUF_CHUNK, KNZ_CHUNK_STRIDE, 1},
-    {KNZ_E_FPAQ, KNZ_ANS1_CHUNK, KNZ_FPAQ_SLOT, 64},
-    {KNZ_E_ANS0, KNZ_HUF_CHUNK, KNZ_ANS_SLOT, 1},
-    {KNZ_E_ANS1, KNZ_ANS1_CHUNK, KNZ_ANS1_SLOT, 64},
-};
-static const EntropyCodec* entropy_codec(uint32_t e) {
-    for (const EntropyCodec& c : kEntropyCodecs) if (c.id == e) return &c;
-    return nullptr;
-}
-static bool entropy_on_device(uint32_t e) { return entropy_codec(e) != nullptr; }
-
+// ---- capabilities: the transforms are the rows of kXfCodecs (knz_transforms.inc), the entropy codecs those of kEntropyCodecs (knz_batch.inc) ----
 extern "C" int knz_supports(uint64_t transform, uint32_t entropy) {
     for (int s = 42; s >= 0; s -= 6) if (!xf_codec((uint32_t)((transform >> s) & 63))) return 0;
     return entropy_on_device(entropy) ? 1 : 0;
@@ -356,271 +323,6 @@ extern "C" uint32_t knz_max_encoded_len(uint64_t transform, uint32_t n) {     //
     for (int s = 42; s >= 0; s -= 6)
         if (const XfCodec* c = xf_codec((uint32_t)((transform >> s) & 63))) req += (c->grow_div && req > 1024) ? req / c->grow_div : c->grow;
     return (uint32_t)std::min<uint64_t>(req, 0xFFFFFFFFu);
-}
-
-// ---- encode batch ----------------------------------------------------------------------------------------------------
-// d_src: nblocks blocks, block b at b*block_size (last one shorter). Output either the framed .knz body/stream
-// (framed=1) or per-block local streams at out_stride bytes (framed=0).
-struct EncodeBatch {
-    const uint8_t* d_src; uint64_t n;
-    uint8_t* d_dst; uint64_t dst_cap;
-    int framed; int with_header; int with_end; int64_t header_input_size;
-    uint64_t out_stride;     // framed == 0
-    int payload_only;        // 1: single EntropyEncoder object, no block header bits
-    uint64_t total_bits;     // result
-};
-
-// block tables of an encode batch: absolute device addresses; blocks <= 15 bytes are copy blocks (CompressedStream.go:773-776)
-struct EncTablesArgs {
-    uint32_t nblocks; uint64_t src; uint64_t n; uint64_t bs; int payload_only; int none_only;
-    uint64_t* blk_off; uint32_t* blk_len; uint32_t* blk_src_len; uint8_t* blk_skip; uint8_t* blk_copy; int32_t* blk_status;
-    uint8_t* active; uint8_t* side;
-};
-__global__ void knz_enc_tables_kernel(EncTablesArgs a) {
-    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= a.nblocks) return;
-    const uint64_t rest = a.n - (uint64_t)b * a.bs;
-    const uint32_t len = (uint32_t)(rest < a.bs ? rest : a.bs);
-    const bool copy = len <= 15 && !a.payload_only;
-    a.blk_off[b] = a.src + (uint64_t)b * a.bs;
-    a.blk_len[b] = len;
-    a.blk_src_len[b] = a.payload_only ? (len > 16 ? len : 16u) : len;   // a bare EntropyEncoder has no copy-block rule
-    a.blk_copy[b] = copy ? 1 : 0;
-    a.blk_skip[b] = (copy || a.none_only) ? 0x7F : 0xFF;                // NullTransform always applies: slot 0 cleared
-    a.blk_status[b] = 0;
-    if (a.active) { a.active[b] = (copy || a.none_only) ? 0 : 1; a.side[b] = 0; }
-}
-
-// the rows of Handle::ResultRow for the blocks of a batch, the totals (bits written, overflow flag) in the row behind the last block
-__global__ void knz_pack_results_kernel(uint32_t nblocks, const uint64_t* written, const uint64_t* cksum, const uint32_t* post_len, const int32_t* status,
-                                        const uint32_t* hdr, const uint8_t* skip, const uint64_t* totals, Handle::ResultRow* rows) {
-    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < nblocks) {
-        Handle::ResultRow r;
-        r.written = written[b]; r.cksum = cksum[b]; r.post_len = post_len[b]; r.status = status[b]; r.mode = hdr[(size_t)b * 6 + 1]; r.skip = skip[b];
-        rows[b] = r;
-    } else if (b == nblocks) {
-        Handle::ResultRow r;
-        r.written = totals[0]; r.cksum = totals[1]; r.post_len = 0; r.status = 0; r.mode = 0; r.skip = 0;
-        rows[b] = r;
-    }
-}
-
-static int encode_batch(Handle* h, EncodeBatch& eb, hipStream_t st) {
-    const knz_cfg& cfg = h->cfg;
-    h->nprobes = 0;
-    if (!knz_supports(cfg.transform, cfg.entropy))
-        return knz_set_error(h, KNZ_ERR_INVALID_CODEC, "transform/entropy combination has no device implementation in this build");
-    const EntropyCodec& ec = *entropy_codec(cfg.entropy);
-    const uint64_t bs = cfg.block_size;
-    const uint32_t nblocks = (uint32_t)((eb.n + bs - 1) / bs);       // (0: Writer.Close on an empty stream, header + end marker only)
-    const uint32_t chunkSize = ec.chunk;
-    const uint32_t maxPost = knz_max_encoded_len(cfg.transform, (uint32_t)std::min<uint64_t>(bs, eb.n ? eb.n : 1));
-    const uint32_t cpb = std::max<uint32_t>(1, (maxPost + chunkSize - 1) / chunkSize);
-    const size_t nslots = (size_t)std::max<uint32_t>(nblocks, 1) * cpb;
-    const uint32_t slotStride = ec.slot_stride;
-
-    if (h->blk_off.reserve(sizeof(uint64_t) * (nblocks + 1)) || h->blk_len.reserve(4 * (nblocks + 1)) ||
-        h->blk_src_len.reserve(4 * (nblocks + 1)) || h->blk_skip.reserve(nblocks + 16) || h->blk_cksum.reserve(8 * (nblocks + 1)) ||
-        h->blk_status.reserve(4 * (nblocks + 1)) || h->unit_bits.reserve(4 * nslots * KNZ_UNITS_PER_CHUNK) || h->unit_src.reserve(4 * nslots * KNZ_UNITS_PER_CHUNK) ||
-        h->scratch.reserve(nslots * (size_t)slotStride + 64) || h->ans_tab.reserve(cfg.entropy == KNZ_E_ANS0 ? nslots * 2048 + nslots * 4 : 16) || h->chunk_rel.reserve(8 * nslots) ||
-        h->blk_written.reserve(8 * (nblocks + 1)) || h->blk_hdr.reserve(4 * 6 * (nblocks + 1)) ||
-        h->blk_dst_bit.reserve(8 * (nblocks + 1)) || h->total_bits.reserve(64) || h->blk_copy.reserve(nblocks + 16))
-        return knz_set_error(h, KNZ_ERR_CREATE_COMPRESSOR, "device workspace allocation failed");
-
-    XfBatch xb;
-    if (nblocks) {   // block tables, filled on the device: no staging copies, no host synchronisation in front of the first kernel
-        const bool noneOnly = cfg.transform == 0;
-        const uint64_t stride = ((uint64_t)maxPost + 64 + 15) & ~(uint64_t)15;
-        if (!noneOnly && xf_alloc(h, xb, nblocks, stride)) return knz_set_error(h, KNZ_ERR_CREATE_COMPRESSOR, "device workspace allocation failed");
-        EncTablesArgs ta;
-        ta.nblocks = nblocks; ta.src = (uint64_t)eb.d_src; ta.n = eb.n; ta.bs = bs; ta.payload_only = eb.payload_only; ta.none_only = noneOnly ? 1 : 0;
-        ta.blk_off = h->blk_off.as<uint64_t>(); ta.blk_len = h->blk_len.as<uint32_t>(); ta.blk_src_len = h->blk_src_len.as<uint32_t>();
-        ta.blk_skip = h->blk_skip.as<uint8_t>(); ta.blk_copy = h->blk_copy.as<uint8_t>(); ta.blk_status = h->blk_status.as<int32_t>();
-        ta.active = noneOnly ? nullptr : xb.active; ta.side = noneOnly ? nullptr : xb.side;
-        hipLaunchKernelGGL(knz_enc_tables_kernel, dim3((nblocks + 255) / 256), dim3(256), 0, st, ta);
-    }
-    const bool skipOpt = (cfg.flags & KNZ_FLAG_SKIP_BLOCKS) != 0 && !eb.payload_only && nblocks != 0;
-    bool hufDirect = false;                                              // Huffman units encoded at their final bit positions (below)
-    HufEncArgs hufArgs;
-    if (skipOpt) {                                                       // -s: incompressible blocks become copy blocks (:778-800)
-        SkipArgs ka;
-        ka.nblocks = nblocks; ka.blk_off = h->blk_off.as<uint64_t>(); ka.blk_len = h->blk_len.as<uint32_t>();
-        ka.blk_copy = h->blk_copy.as<uint8_t>(); ka.blk_skip = h->blk_skip.as<uint8_t>(); ka.active = cfg.transform != 0 ? xb.active : nullptr;
-        hipLaunchKernelGGL(knz_skip_detect_kernel, dim3(nblocks), dim3(256), 0, st, ka);
-    }
-    hipEventRecord(h->ev[0], st);
-    if (nblocks && cfg.checksum_bits != 0) {        // checksum of the untransformed block (encodingTask.encode :760-767)
-        XxhArgs xa;
-        xa.nblocks = nblocks; xa.ptr = h->blk_off.as<uint64_t>(); xa.len = h->blk_len.as<uint32_t>(); xa.cksum = h->blk_cksum.as<uint64_t>();
-        xa.status = h->blk_status.as<int32_t>(); xa.mode = nullptr; xa.bits = cfg.checksum_bits; xa.verify = 0;
-        hipLaunchKernelGGL(knz_xxhash_kernel, dim3(nblocks), dim3(64), 0, st, xa);
-    }
-    if (nblocks && cfg.transform != 0) {
-        xb.cur_ptr = h->blk_off.as<uint64_t>(); xb.cur_len = h->blk_len.as<uint32_t>(); xb.skip = h->blk_skip.as<uint8_t>();
-        xb.blk_status = h->blk_status.as<int32_t>();
-        bool hasUtf = false;                                             // (a stage that reads or writes ctx["dataType"])
-        for (int sft = 42; sft >= 0; sft -= 6) hasUtf = hasUtf || xf_codec((uint32_t)((cfg.transform >> sft) & 63))->data_type;
-        if (hasUtf) {                                                    // ctx["dataType"] from the magic number of the untransformed block (:811-819)
-            if (h->blk_dt.reserve(nblocks + 16)) return knz_set_error(h, KNZ_ERR_CREATE_COMPRESSOR, "device workspace allocation failed");
-            hipLaunchKernelGGL(knz_block_datatype_kernel, dim3((nblocks + 63) / 64), dim3(64), 0, st, nblocks, (const uint64_t*)h->blk_off.as<uint64_t>(),
-                               (const uint32_t*)h->blk_len.as<uint32_t>(), h->blk_dt.as<uint8_t>());
-            xb.blk_dt = h->blk_dt.as<uint8_t>();
-        }
-        int rc = forward_sequence(h, xb, cfg.transform, st);
-        if (rc) return rc;
-    }
-    hipEventRecord(h->ev[1], st);
-    if (nblocks) {
-        if (cfg.entropy == KNZ_E_HUFFMAN || cfg.entropy == KNZ_E_NONE) {
-            HufEncArgs a;
-            a.data = nullptr; a.blk_off = h->blk_off.as<uint64_t>(); a.blk_len = h->blk_len.as<uint32_t>();
-            a.chunks_per_block = cpb; a.scratch = h->scratch.as<uint8_t>(); a.unit_bits = h->unit_bits.as<uint32_t>(); a.unit_src = h->unit_src.as<uint32_t>();
-            a.blk_status = h->blk_status.as<int32_t>();
-            if (cfg.entropy == KNZ_E_HUFFMAN) {
-                const uint32_t nc = nblocks * cpb, groups = (nc + 63) / 64;
-                if (h->huf_stfreq.reserve((size_t)groups * 256 * 64 * 2) || h->huf_stsym.reserve((size_t)groups * 256 * 64) ||
-                    h->huf_stlen.reserve((size_t)groups * 256 * 64) || h->huf_stcnt.reserve((size_t)groups * 64 * 2) || h->huf_stmax.reserve((size_t)groups * 64))
-                    return knz_set_error(h, KNZ_ERR_CREATE_COMPRESSOR, "device workspace allocation failed");
-                a.st_freq = h->huf_stfreq.as<uint16_t>(); a.st_sym = h->huf_stsym.as<uint8_t>(); a.st_len = h->huf_stlen.as<uint8_t>();
-                a.st_count = h->huf_stcnt.as<uint16_t>(); a.st_maxlen = h->huf_stmax.as<uint8_t>(); a.nchunks = nc;
-                // The units are encoded at their final bit positions (sizes pass -> layout scans -> encoder, further down) unless copy blocks of -s
-                // have to overwrite chunks afterwards or the test switch asks for the scratch-slot form (units to slots, knz_gather_kernel).
-                hufDirect = !skipOpt && knz_test_switch("KNZ_HUF_SCRATCH") == nullptr;
-                a.st_fhist = nullptr; a.dst_words = nullptr; a.chunk_rel = nullptr; a.blk_dst_bit = nullptr; a.total_bits = nullptr;
-                if (hufDirect) {
-                    if (h->huf_fhist.reserve((size_t)nc * 4 * 256 * 2 + 64)) return knz_set_error(h, KNZ_ERR_CREATE_COMPRESSOR, "device workspace allocation failed");
-                    a.st_fhist = h->huf_fhist.as<uint16_t>();
-                }
-                KNZ_LAUNCH_PROBED(knz_huf_hist_kernel, dim3(nc), dim3(256), 0, st, a);
-                KNZ_LAUNCH_PROBED(knz_huf_lengths_kernel, dim3(groups), dim3(64), 0, st, a);
-                if (hufDirect) { KNZ_LAUNCH_PROBED(knz_huf_encode_kernel<true>, dim3(nc), dim3(256), 0, st, a); hufArgs = a; }
-                else KNZ_LAUNCH_PROBED(knz_huf_encode_kernel<false>, dim3(nc), dim3(256), 0, st, a);
-            }
-            else hipLaunchKernelGGL(knz_raw_units_kernel, dim3(nblocks * cpb), dim3(256), 0, st, a);
-        } else if (cfg.entropy == KNZ_E_FPAQ) {
-            FpaqArgs a;
-            a.blk_off = h->blk_off.as<uint64_t>(); a.blk_len = h->blk_len.as<uint32_t>(); a.blk_src_len = h->blk_src_len.as<uint32_t>();
-            a.chunks_per_block = cpb; a.scratch = h->scratch.as<uint8_t>(); a.unit_bits = h->unit_bits.as<uint32_t>();
-            a.unit_src = h->unit_src.as<uint32_t>(); a.blk_status = h->blk_status.as<int32_t>();
-            KNZ_LAUNCH_PROBED(knz_fpaq_encode_kernel, dim3(nblocks), dim3(64), 0, st, a);
-        } else if (cfg.entropy == KNZ_E_ANS1) {
-            // bounded groups of blocks (like the UTF stage and the suffix sort): a chunk slot takes 768 KiB of count / coder tables, 112 KiB of
-            // context headers and the 64 MiB expanded-step stream; the workspace is sized to at most ~64 GiB of them (up to ~960 chunks side by side: the chains of a group run as one wave each, 25 ms whatever their number), not to the batch
-            const size_t perSlot = (size_t)65536 * 12 + (size_t)256 * KNZ_ANS1_CTXHDR_BYTES + 1024 + KNZ_ANS1_ENT_STRIDE * 16;
-            const uint32_t slotsPerGroup = (uint32_t)std::max<size_t>(cpb, std::min<size_t>((size_t)nblocks * cpb, ((size_t)64 << 30) / perSlot));
-            uint32_t GB = std::max<uint32_t>(1, slotsPerGroup / cpb);                   // whole blocks per group
-            if (const char* e = knz_test_switch("KNZ_ANS1_GROUP_BLOCKS")) GB = std::max(1, atoi(e));   // (tests: several groups on small inputs)
-            const bool ans1EncPlain = knz_test_switch("KNZ_ANS1_ENC_PLAIN") != nullptr;   // (A/B and cross-check: the compiler's loop instead of the hand-written one)
-            // a group the device has no room for (other handles, a smaller device) is halved until it fits: fewer chains side by side, same bytes
-            uint32_t gs = GB * cpb;
-            for (;;) {
-                gs = GB * cpb;
-                if (!(h->a1_freqs.reserve((size_t)gs * 65536 * 4) || h->a1_tab.reserve((size_t)gs * 65536 * 8) ||
-                      h->a1_ctxhdr.reserve((size_t)gs * 256 * KNZ_ANS1_CTXHDR_BYTES + 64) || h->a1_ctxbits.reserve((size_t)gs * 256 * 4) ||
-                      h->a1_ent.reserve((size_t)gs * KNZ_ANS1_ENT_STRIDE * 16)))
-                    break;
-                if (GB == 1) return knz_set_error(h, KNZ_ERR_CREATE_COMPRESSOR, "device workspace allocation failed");
-                h->a1_freqs.release(); h->a1_tab.release(); h->a1_ctxhdr.release(); h->a1_ctxbits.release(); h->a1_ent.release();
-                GB = (GB + 1) / 2;
-            }
-            for (uint32_t b0 = 0; b0 < nblocks; b0 += GB) {
-                const uint32_t gb = std::min<uint32_t>(GB, nblocks - b0), ns = gb * cpb;
-                const size_t s0 = (size_t)b0 * cpb;
-                Ans1Args a;                                                                // the group's slice of every per-block / per-slot table
-                a.blk_off = h->blk_off.as<uint64_t>() + b0; a.blk_len = h->blk_len.as<uint32_t>() + b0; a.chunks_per_block = cpb; a.nslots = ns;
-                a.scratch = h->scratch.as<uint8_t>() + s0 * slotStride; a.unit_bits = h->unit_bits.as<uint32_t>() + s0 * 5; a.unit_src = h->unit_src.as<uint32_t>() + s0 * 5;
-                a.freqs = h->a1_freqs.as<uint32_t>(); a.tab = h->a1_tab.as<uint2>(); a.ctx_hdr = h->a1_ctxhdr.as<uint8_t>();
-                a.ctx_bits = h->a1_ctxbits.as<uint32_t>(); a.blk_status = h->blk_status.as<int32_t>() + b0;
-                hipMemsetAsync(h->a1_freqs.p, 0, (size_t)ns * 65536 * 4, st);
-                KNZ_LAUNCH_PROBED(knz_ans1_hist_kernel, dim3(ns * KNZ_ANS1_HIST_WGS * KNZ_ANS1_HIST_SLICES), dim3(256), 0, st, a);
-                hipLaunchKernelGGL(knz_ans1_stats_kernel, dim3(ns * 256), dim3(64), 0, st, a);
-                hipLaunchKernelGGL(knz_ans1_merge_kernel, dim3(ns), dim3(256), 0, st, a);
-                KNZ_LAUNCH_PROBED(knz_ans1_expand_kernel, dim3(ns, 128), dim3(256), 0, st, a, h->a1_ent.as<uint4>());
-#ifndef KNZ_HIP_EMU
-                if (!ans1EncPlain) KNZ_LAUNCH_PROBED(knz_ans1_encode_asm_kernel, dim3(ns), dim3(64), 0, st, a, (const uint4*)h->a1_ent.as<uint4>());
-                else
-#endif
-                KNZ_LAUNCH_PROBED(knz_ans1_encode_kernel, dim3(ns), dim3(64), 0, st, a, (const uint4*)h->a1_ent.as<uint4>());
-            }
-        } else if (cfg.entropy == KNZ_E_ANS0) {
-            Ans0Args a;
-            a.data = nullptr; a.blk_off = h->blk_off.as<uint64_t>(); a.blk_len = h->blk_len.as<uint32_t>();
-            a.chunks_per_block = cpb; a.scratch = h->scratch.as<uint8_t>(); a.unit_bits = h->unit_bits.as<uint32_t>(); a.unit_src = h->unit_src.as<uint32_t>();
-            a.tab = h->ans_tab.as<uint2>(); a.chunk_info = (uint32_t*)(h->ans_tab.as<uint8_t>() + nslots * 2048);
-            a.blk_status = h->blk_status.as<int32_t>();
-            const uint32_t ns = nblocks * cpb;
-            hipLaunchKernelGGL(knz_ans0_stats_kernel, dim3(ns), dim3(256), 0, st, a);
-            KNZ_LAUNCH_PROBED(knz_ans0_encode_kernel, dim3((ns + KNZ_ANS0_CHUNKS_PER_WG - 1) / KNZ_ANS0_CHUNKS_PER_WG), dim3(128), 0, st, a, ns);
-        }
-    }
-    hipEventRecord(h->ev[2], st);
-    if (skipOpt && cfg.entropy != KNZ_E_NONE) {
-        CopyUnitsArgs ca;
-        ca.chunks_per_block = cpb; ca.chunk_size = chunkSize; ca.blk_copy = h->blk_copy.as<uint8_t>(); ca.blk_off = h->blk_off.as<uint64_t>();
-        ca.blk_len = h->blk_len.as<uint32_t>(); ca.scratch = h->scratch.as<uint8_t>(); ca.slot_stride = slotStride;
-        ca.unit_bits = h->unit_bits.as<uint32_t>(); ca.unit_src = h->unit_src.as<uint32_t>(); ca.blk_status = h->blk_status.as<int32_t>();
-        hipLaunchKernelGGL(knz_copy_units_kernel, dim3(nblocks * cpb), dim3(256), 0, st, ca);
-    }
-    LayoutArgs la;
-    uint32_t toks[8];
-    la.nblocks = nblocks; la.chunks_per_block = cpb; la.unit_bits = h->unit_bits.as<uint32_t>();
-    la.blk_len = h->blk_len.as<uint32_t>(); la.blk_src_len = h->blk_src_len.as<uint32_t>(); la.blk_skip = h->blk_skip.as<uint8_t>(); la.blk_copy = h->blk_copy.as<uint8_t>();
-    la.blk_cksum = h->blk_cksum.as<uint64_t>(); la.checksum_bits = cfg.checksum_bits; la.n_transforms = (uint32_t)seq_tokens(cfg.transform, toks);
-    la.chunk_size = chunkSize; la.payload_only = eb.payload_only; la.chunk_rel = h->chunk_rel.as<uint64_t>(); la.blk_written = h->blk_written.as<uint64_t>();
-    la.blk_hdr = h->blk_hdr.as<uint32_t>();
-    if (nblocks) hipLaunchKernelGGL(knz_layout_blocks_kernel, dim3(nblocks), dim3(256), 0, st, la);
-
-    StreamArgs sa;
-    sa.nblocks = nblocks; sa.chunks_per_block = cpb; sa.chunk_size = chunkSize; sa.blk_len = h->blk_len.as<uint32_t>();
-    sa.chunk_rel = h->chunk_rel.as<uint64_t>(); sa.blk_written = h->blk_written.as<uint64_t>(); sa.blk_hdr = h->blk_hdr.as<uint32_t>();
-    sa.dst_words = (uint32_t*)eb.d_dst;
-    const uint64_t usable = eb.dst_cap >= 8 ? ((eb.dst_cap & ~(uint64_t)3) - 4) : 0;   // whole BE words are stored
-    sa.dst_cap_bits = usable * 8;
-    sa.first_bit = 0; sa.framed = eb.framed; sa.block_stride_bits = eb.out_stride * 8; sa.end_marker = eb.with_end;
-    sa.header_bits = 0;
-    for (int i = 0; i < 8; i++) sa.header_words[i] = 0;
-    if (eb.framed && eb.with_header) sa.header_bits = knz_build_stream_header(cfg, eb.header_input_size, sa.header_words);
-    sa.blk_dst_bit = h->blk_dst_bit.as<uint64_t>(); sa.total_bits = h->total_bits.as<uint64_t>();
-    sa.blk_status = h->blk_status.as<int32_t>();
-    hipLaunchKernelGGL(knz_layout_stream_kernel, dim3(1), dim3(256), 0, st, sa);
-    hipEventRecord(h->ev[3], st);
-    if (hufDirect && nblocks) {                                          // Huffman: the encoder itself places the units (no scratch round trip, no gather)
-        hufArgs.dst_words = (uint32_t*)eb.d_dst; hufArgs.chunk_rel = h->chunk_rel.as<uint64_t>(); hufArgs.blk_dst_bit = h->blk_dst_bit.as<uint64_t>();
-        hufArgs.total_bits = h->total_bits.as<uint64_t>();
-        KNZ_LAUNCH_PROBED(knz_huf_encode_kernel<false>, dim3(nblocks * cpb), dim3(256), 0, st, hufArgs);
-    }
-
-    GatherArgs ga;
-    ga.chunks_per_block = cpb; ga.chunk_size = chunkSize; ga.blk_len = h->blk_len.as<uint32_t>(); ga.unit_bits = h->unit_bits.as<uint32_t>();
-    ga.scratch = h->scratch.as<uint8_t>(); ga.chunk_stride = slotStride;
-    ga.unit_src = h->unit_src.as<uint32_t>();
-    ga.chunk_rel = h->chunk_rel.as<uint64_t>(); ga.blk_dst_bit = h->blk_dst_bit.as<uint64_t>(); ga.dst_words = (uint32_t*)eb.d_dst;
-    ga.total_bits = h->total_bits.as<uint64_t>();
-    if (nblocks && !hufDirect) KNZ_LAUNCH_PROBED(knz_gather_kernel, dim3(nblocks * cpb, ec.gather_y), dim3(256), 0, st, ga);
-    hipEventRecord(h->ev[4], st);
-    h->ev_valid = true;
-
-    // results come back packed: one row per block (bit count, checksum, post-transform length, status, mode, skip flags) and the batch totals, gathered
-    // by one small kernel and brought over by ONE asynchronous copy into pinned memory, one synchronisation
-    if (h->res_rows.reserve(sizeof(Handle::ResultRow) * ((size_t)nblocks + 1)) || h->reserve_pinned_rows((size_t)nblocks))
-        return knz_set_error(h, KNZ_ERR_CREATE_COMPRESSOR, "pinned host allocation failed");
-    hipLaunchKernelGGL(knz_pack_results_kernel, dim3((nblocks + 1 + 255) / 256), dim3(256), 0, st, nblocks, (const uint64_t*)h->blk_written.as<uint64_t>(),
-                       (const uint64_t*)h->blk_cksum.as<uint64_t>(), (const uint32_t*)h->blk_len.as<uint32_t>(), (const int32_t*)h->blk_status.as<int32_t>(),
-                       (const uint32_t*)h->blk_hdr.as<uint32_t>(), (const uint8_t*)h->blk_skip.as<uint8_t>(), (const uint64_t*)h->total_bits.as<uint64_t>(),
-                       h->res_rows.as<Handle::ResultRow>());
-    Handle::ResultRow* rows = h->pinned_rows;
-    HIP_OK(hipMemcpyAsync(rows, h->res_rows.p, sizeof(Handle::ResultRow) * ((size_t)nblocks + 1), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    HIP_OK(hipGetLastError());
-    if (rows[nblocks].cksum != 0) return knz_set_error(h, KNZ_ERR_WRITE_FILE, "destination buffer too small");     // (the totals row: bits, overflow flag)
-    for (uint32_t b = 0; b < nblocks; b++)
-        if (rows[b].status != 0) return knz_set_error(h, rows[b].status, "block failed (the reference panics on this input: ERR_PROCESS_BLOCK)");
-    eb.total_bits = rows[nblocks].written;
-    h->post_bytes = 0;
-    for (uint32_t b = 0; b < nblocks; b++) h->post_bytes += rows[b].post_len;
-    for (int i = 0; i < 8; i++) h->stage_bytes[i] = (nblocks && cfg.transform != 0) ? ((const uint64_t*)((const uint8_t*)h->pinned + 3072))[i] : 0;
-    return KNZ_OK;
 }
 
 extern "C" int knz_dev_compress(void* handle, const void* d_src, uint64_t n, int64_t header_input_size, void* d_dst,

@@ -784,7 +784,7 @@ def check_rank_pipe(be, monkeypatch, sizes=((50000, 1 << 14), (300000, 1 << 16),
                     sp, k1 = be.to_dev(stream)
                     res = {}
                     for form in forms:
-                        for v in ("KNZ_NO_RANK_PIPE", "KNZ_RANK_UNPACKED", "KNZ_RANK_CUT", "KNZ_RANK_PIPE_TWO_GROUPS"):
+                        for v in ("KNZ_NO_RANK_PIPE", "KNZ_RANK_UNPACKED", "KNZ_RANK_CUT", "KNZ_RANK_PIPE_TWO_GROUPS", "KNZ_RANK_PIPE_ONE_GROUP"):
                             monkeypatch.delenv(v, raising=False)
                         if form == "regular":
                             monkeypatch.setenv("KNZ_NO_RANK_PIPE", "1")
@@ -794,6 +794,8 @@ def check_rank_pipe(be, monkeypatch, sizes=((50000, 1 << 14), (300000, 1 << 16),
                             monkeypatch.setenv("KNZ_RANK_CUT", "512")
                         elif form == "two_groups":                                         # (the long chains in a launch of their own, the stages behind the chain in two passes)
                             monkeypatch.setenv("KNZ_RANK_PIPE_TWO_GROUPS", "1")
+                        elif form == "one_group":                                          # (every chain in one launch, one pass behind it, also where the lengths would split the batch)
+                            monkeypatch.setenv("KNZ_RANK_PIPE_ONE_GROUP", "1")
                         c = K.Codec(seq, "ANS1", bs, lib=be.lib)
                         out, ko = be.empty(n2 + 4096)
                         nd = c.dev_decompress(sp, len(stream), out, n2 + 4096)
@@ -804,7 +806,7 @@ def check_rank_pipe(be, monkeypatch, sizes=((50000, 1 << 14), (300000, 1 << 16),
                     assert len({v for k, v in res.items() if k != "regular"}) == 1, res
                     if name in ("corpus", "sparse", "steps"):
                         assert res["pipe"] >= 1, (seq, n, bs, seed, name, "no block took the fused chain")
-    for v in ("KNZ_NO_RANK_PIPE", "KNZ_RANK_UNPACKED", "KNZ_RANK_CUT", "KNZ_RANK_PIPE_TWO_GROUPS"):
+    for v in ("KNZ_NO_RANK_PIPE", "KNZ_RANK_UNPACKED", "KNZ_RANK_CUT", "KNZ_RANK_PIPE_TWO_GROUPS", "KNZ_RANK_PIPE_ONE_GROUP"):
         monkeypatch.delenv(v, raising=False)
 
 

@@ -335,6 +335,8 @@ def test_bwt_suffix_sort_fuzz(be, monkeypatch):
 def test_rank_pipe_under_ans1_decoder(be, monkeypatch):
     # (blocks of 6 MiB: two rANS chunks per block, the chain waits on the first quarter of the first and on the whole second)
     P.check_rank_pipe(be, monkeypatch, sizes=((50000, 1 << 14), (3000000, 1 << 20), (13000001, 6 << 20)), seeds=(5,))
+    # (a short last block: the lengths split these batches into two launches, the switch keeps them in one)
+    P.check_rank_pipe(be, monkeypatch, sizes=((50000, 1 << 14), (200001, 1 << 17)), seeds=(5,), forms=("pipe", "regular", "one_group"))
     P.check_corrupt_streams(be, trials=6)
 
 
