@@ -125,6 +125,34 @@ int knz_dev_decompress(void* handle, const void* d_src, uint64_t n_bytes,
                        void* d_dst, uint64_t dst_cap, uint64_t* out_bytes, void* hip_stream);
 
 /*
+ * Many independent streams in ONE device batch: what a host that compresses a tree of files (one .knz stream per file) calls instead of
+ * K times knz_dev_compress / knz_dev_decompress. All blocks of all streams run side by side through one batch; every pointer of a
+ * knz_stream is a DEVICE pointer, the array itself is host memory.
+ *   compress:   d_dst[0 .. out_bytes) of stream k is byte for byte what knz_dev_compress(handle, d_src, n, header_input_size, ...) writes
+ *               for that input alone (its own header with its own size field, block framing, skip flags, checksums, copy blocks, end
+ *               marker; n == 0 gives the header and the end marker, as there). d_src is 16-byte aligned, d_dst 4-byte aligned.
+ *   decompress: stream k gives the bytes and out_bytes of knz_dev_decompress for it alone, or that call's error code in status. Every
+ *               stream's header is parsed; all streams of a call carry the transform, entropy codec, block size and checksum size of the
+ *               first stream whose header parses: one that does not gets KNZ_ERR_INVALID_PARAM. Short inner blocks are placed per stream.
+ *   results:    the call returns 0 or the status of the first stream (lowest index) that failed. A stream that fails (damaged, too small
+ *               a destination: KNZ_ERR_WRITE_FILE) never keeps the others from completing, and nothing is written behind any dst_cap.
+ *               dst_cap follows the single calls' rule (whole big-endian words are stored: the stream plus up to 7 bytes must fit).
+ *   counters:   knz_last_counter / knz_last_kernel_times report the one batch (KNZ_COUNTER_POST_TRANSFORM_BYTES: the sum over the streams).
+ *   workspace:  a stream list whose workspace the device refuses is taken in halves. On a handle of several lanes the call runs on the
+ *               lane that owns streams[0].d_dst; a stream whose d_dst lives on another device gets KNZ_ERR_INVALID_PARAM.
+ *   n <= 0 returns 0. There is no limit on n or on the number of blocks beyond the batch's own.
+ */
+typedef struct {
+    const void* d_src; uint64_t n;    /* compress: the input bytes (n may be 0) ; decompress: one .knz stream, 4-byte aligned, readable to the next multiple of 4 */
+    void* d_dst; uint64_t dst_cap;    /* 4-byte aligned, same rules as knz_dev_compress / knz_dev_decompress */
+    int64_t header_input_size;        /* compress: ctx["fileSize"] for this stream's header (0 = unknown) ; decompress: ignored */
+    uint64_t out_bytes;               /* result */
+    int32_t status; int32_t reserved; /* result: 0 or this stream's kanzi error code */
+} knz_stream;
+int knz_dev_compress_many(void* handle, knz_stream* streams, int n, void* hip_stream);
+int knz_dev_decompress_many(void* handle, knz_stream* streams, int n, void* hip_stream);
+
+/*
  * Multi-GPU block sharding: a rank encodes blocks [first_block, first_block+n_blocks) of a
  * stream whose blocks are block_size bytes each; d_src points at this rank's first block. The result is a
  * bit string (no stream header, no end marker): *out_bits bits, zero padded to a byte in d_dst.

@@ -52,6 +52,11 @@ class _Block(C.Structure):
                 ("reserved", C.c_uint16), ("checksum", C.c_uint64), ("status", C.c_int32), ("reserved2", C.c_int32)]
 
 
+class _Stream(C.Structure):
+    _fields_ = [("d_src", C.c_void_p), ("n", C.c_uint64), ("d_dst", C.c_void_p), ("dst_cap", C.c_uint64),
+                ("header_input_size", C.c_int64), ("out_bytes", C.c_uint64), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
 def library_path():
     return os.environ.get("KNZ_GPU_LIB", os.path.join(_HERE, "libknz_gpu.so"))
 
@@ -96,6 +101,8 @@ def load_library(path=None):
     L.knz_decode_blocks.argtypes = [vp, C.POINTER(_Block), C.c_int]
     L.knz_dev_compress.argtypes = [vp, vp, C.c_uint64, C.c_int64, vp, C.c_uint64, u64p, vp]
     L.knz_dev_decompress.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, vp]
+    L.knz_dev_compress_many.argtypes = [vp, C.POINTER(_Stream), C.c_int, vp]
+    L.knz_dev_decompress_many.argtypes = [vp, C.POINTER(_Stream), C.c_int, vp]
     L.knz_dev_compress_blocks.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, vp]
     L.knz_dev_decompress_blocks.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, vp]
     L.knz_dev_assemble.argtypes = [vp, C.c_int64, C.POINTER(vp), u64p, C.c_int, vp, C.c_uint64, u64p, vp]
@@ -171,6 +178,28 @@ class Codec:
         out = C.c_uint64()
         self._chk(self.L.knz_dev_decompress(self.h, d_src, n_bytes, d_dst, dst_cap, C.byref(out), stream))
         return out.value
+
+    def _many(self, fn, items, check, stream):
+        n = len(items)
+        arr = (_Stream * max(n, 1))()
+        for i, it in enumerate(items):
+            arr[i].d_src, arr[i].n, arr[i].d_dst, arr[i].dst_cap = it[0], it[1], it[2], it[3]
+            arr[i].header_input_size = it[4] if len(it) > 4 and it[4] is not None else (it[1] if fn is self.L.knz_dev_compress_many else 0)
+        rc = fn(self.h, arr, n, stream)
+        self.last_many_rc = rc
+        if check:
+            self._chk(rc)
+        return [(int(arr[i].out_bytes), int(arr[i].status)) for i in range(n)]
+
+    def dev_compress_many(self, items, check=False, stream=0):
+        """items: [(d_src, n, d_dst, dst_cap[, header_input_size])], one .knz stream each, all their blocks in one device batch
+        (knz_dev_compress_many). Returns [(out_bytes, status)] per stream; the call's own return value is in last_many_rc. Raises only with
+        check=True (the first failing stream's code). header_input_size defaults to n, as in dev_compress."""
+        return self._many(self.L.knz_dev_compress_many, items, check, stream)
+
+    def dev_decompress_many(self, items, check=False, stream=0):
+        """items: [(d_src, n_bytes, d_dst, dst_cap)], one .knz stream each (knz_dev_decompress_many). Returns [(out_bytes, status)]."""
+        return self._many(self.L.knz_dev_decompress_many, items, check, stream)
 
     def dev_compress_blocks(self, d_src, n, d_dst, dst_cap, stream=0):
         out = C.c_uint64()

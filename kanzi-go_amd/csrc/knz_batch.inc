@@ -12,6 +12,9 @@ struct EncodeBatch {
     uint64_t out_stride;     // framed == 0
     int payload_only;        // 1: single EntropyEncoder object, no block header bits
     uint64_t total_bits;     // result
+    // several streams in one batch (knz_many.inc; framed == 0): the blocks are those of a table of streams, many_blocks of them, none longer than
+    // many_max_len; a block that fails leaves its status in blk_status for the caller instead of failing the batch
+    const ManyStream* many = nullptr; uint32_t many_streams = 0, many_blocks = 0, many_max_len = 0; uint32_t* many_blk_stream = nullptr;
 };
 
 // ---- decode batch ---------------------------------------------------------------------------------------------------
@@ -29,6 +32,9 @@ struct DecodeBatch {
     std::vector<uint64_t> end_bit;
     std::vector<int32_t> status;
     uint64_t total_out;
+    // several streams in one batch (knz_many.inc): every failing block is marked in `status`, not only the first ; done: the batch ran to its end
+    // (a block that failed then leaves the others as they are)
+    bool many = false, done = false;
     // a framed stream with the codec parameters of `c` (the handle's, or a stream header's), blocks placed at block_size: call sites state what differs
     DecodeBatch(const knz_cfg& c, const uint8_t* stream, uint64_t n, uint8_t* out, uint64_t cap)
         : d_stream(stream), nbytes(n), framed(1), first_bit(0), seg_bits(0), nblocks(0), d_out(out), out_cap(cap), out_stride(c.block_size),
@@ -406,6 +412,24 @@ __global__ void knz_enc_tables_kernel(EncTablesArgs a) {
     if (a.active) { a.active[b] = (copy || a.none_only) ? 0 : 1; a.side[b] = 0; }
 }
 
+// ... of a batch over several streams: block b is block b - first_block of the stream that owns it
+__global__ void knz_many_enc_tables_kernel(EncTablesArgs a, const ManyStream* s, uint32_t K, uint32_t* blk_stream) {
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= a.nblocks) return;
+    const uint32_t k = knz_many_owner(s, K, b);
+    const uint64_t at = (uint64_t)(b - s[k].first_block) * a.bs, rest = s[k].n - at;
+    const uint32_t len = (uint32_t)(rest < a.bs ? rest : a.bs);
+    const bool copy = len <= 15;
+    blk_stream[b] = k;
+    a.blk_off[b] = s[k].src + at;
+    a.blk_len[b] = len;
+    a.blk_src_len[b] = len;
+    a.blk_copy[b] = copy ? 1 : 0;
+    a.blk_skip[b] = (copy || a.none_only) ? 0x7F : 0xFF;
+    a.blk_status[b] = 0;
+    if (a.active) { a.active[b] = (copy || a.none_only) ? 0 : 1; a.side[b] = 0; }
+}
+
 // the rows of Handle::ResultRow for the blocks of a batch, the totals (bits written, overflow flag) in the row behind the last block
 __global__ void knz_pack_results_kernel(uint32_t nblocks, const uint64_t* written, const uint64_t* cksum, const uint32_t* post_len, const int32_t* status,
                                         const uint32_t* hdr, const uint8_t* skip, const uint64_t* totals, Handle::ResultRow* rows) {
@@ -428,9 +452,9 @@ static int encode_batch(Handle* h, EncodeBatch& eb, hipStream_t st) {
         return knz_set_error(h, KNZ_ERR_INVALID_CODEC, "transform/entropy combination has no device implementation in this build");
     const EntropyCodec& ec = *entropy_codec(cfg.entropy);
     const uint64_t bs = cfg.block_size;
-    const uint32_t nblocks = (uint32_t)((eb.n + bs - 1) / bs);       // (0: Writer.Close on an empty stream, header + end marker only)
+    const uint32_t nblocks = eb.many ? eb.many_blocks : (uint32_t)((eb.n + bs - 1) / bs);       // (0: Writer.Close on an empty stream, header + end marker only)
     const uint32_t chunkSize = ec.chunk;
-    const uint32_t maxPost = knz_max_encoded_len(cfg.transform, (uint32_t)std::min<uint64_t>(bs, eb.n ? eb.n : 1));
+    const uint32_t maxPost = knz_max_encoded_len(cfg.transform, eb.many ? std::max<uint32_t>(eb.many_max_len, 1) : (uint32_t)std::min<uint64_t>(bs, eb.n ? eb.n : 1));
     const uint32_t cpb = std::max<uint32_t>(1, (maxPost + chunkSize - 1) / chunkSize);
     const size_t nslots = (size_t)std::max<uint32_t>(nblocks, 1) * cpb;
     const uint32_t slotStride = ec.slot_stride;
@@ -453,7 +477,8 @@ static int encode_batch(Handle* h, EncodeBatch& eb, hipStream_t st) {
         ta.blk_off = h->blk_off.as<uint64_t>(); ta.blk_len = h->blk_len.as<uint32_t>(); ta.blk_src_len = h->blk_src_len.as<uint32_t>();
         ta.blk_skip = h->blk_skip.as<uint8_t>(); ta.blk_copy = h->blk_copy.as<uint8_t>(); ta.blk_status = h->blk_status.as<int32_t>();
         ta.active = noneOnly ? nullptr : xb.active; ta.side = noneOnly ? nullptr : xb.side;
-        hipLaunchKernelGGL(knz_enc_tables_kernel, dim3((nblocks + 255) / 256), dim3(256), 0, st, ta);
+        if (eb.many) hipLaunchKernelGGL(knz_many_enc_tables_kernel, dim3((nblocks + 255) / 256), dim3(256), 0, st, ta, eb.many, eb.many_streams, eb.many_blk_stream);
+        else hipLaunchKernelGGL(knz_enc_tables_kernel, dim3((nblocks + 255) / 256), dim3(256), 0, st, ta);
     }
     const bool skipOpt = (cfg.flags & KNZ_FLAG_SKIP_BLOCKS) != 0 && !eb.payload_only && nblocks != 0;
     if (skipOpt) {                                                       // -s: incompressible blocks become copy blocks (:778-800)
@@ -545,7 +570,7 @@ static int encode_batch(Handle* h, EncodeBatch& eb, hipStream_t st) {
     HIP_OK(hipStreamSynchronize(st));
     HIP_OK(hipGetLastError());
     if (rows[nblocks].cksum != 0) return knz_set_error(h, KNZ_ERR_WRITE_FILE, "destination buffer too small");     // (the totals row: bits, overflow flag)
-    for (uint32_t b = 0; b < nblocks; b++)
+    for (uint32_t b = 0; b < nblocks && !eb.many; b++)
         if (rows[b].status != 0) return knz_set_error(h, rows[b].status, "block failed (the reference panics on this input: ERR_PROCESS_BLOCK)");
     eb.total_bits = rows[nblocks].written;
     h->post_bytes = 0;
@@ -655,13 +680,18 @@ static int dec_place_outputs(Handle* h, DecStage& d, hipStream_t st) {
     HIP_OK(hipMemcpyAsync(db.pre_len.data(), h->blk_len.p, 4 * (size_t)nblocks, hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(db.status.data(), h->blk_status.p, 4 * (size_t)nblocks, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
+    int first = KNZ_OK;
     for (uint32_t b = 0; b < nblocks; b++) {
-        if (db.status[b]) return knz_set_error(h, db.status[b], "invalid block in stream");
-        if (xf) { if (db.pre_len[b] > xstride) return knz_set_error(h, KNZ_ERR_BLOCK_SIZE, "block larger than the decoder buffers"); continue; }
-        int rc = dec_block_fits(h, db, b);
-        if (rc) return rc;
+        int rc = KNZ_OK;
+        if (db.status[b]) rc = knz_set_error(h, db.status[b], "invalid block in stream");
+        else if (xf) { if (db.pre_len[b] > xstride) rc = knz_set_error(h, KNZ_ERR_BLOCK_SIZE, "block larger than the decoder buffers"); }
+        else rc = dec_block_fits(h, db, b);
+        if (!rc) continue;
+        db.status[b] = rc;
+        if (!db.many) return rc;
+        if (!first) first = rc;
     }
-    return KNZ_OK;
+    return first;
 }
 
 // Inverse transforms and copy-out: the stages the fused chain has not done, in one pass or (the chain in two launches) two; then the blocks to where the
@@ -697,12 +727,16 @@ static int dec_inverse_transforms(Handle* h, DecStage& d, hipStream_t st) {
     HIP_OK(hipMemcpyAsync(db.status.data(), h->blk_status.p, 4 * (size_t)nblocks, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     std::vector<uint64_t> dstp(nblocks);
+    int first = KNZ_OK;
     for (uint32_t b = 0; b < nblocks; b++) {
-        if (db.status[b]) return knz_set_error(h, db.status[b], "inverse transform failed");
-        rc = dec_block_fits(h, db, b);
-        if (rc) return rc;
+        rc = db.status[b] ? knz_set_error(h, db.status[b], "inverse transform failed") : dec_block_fits(h, db, b);
         dstp[b] = (uint64_t)db.d_out + (uint64_t)b * db.out_stride;
+        if (!rc) continue;
+        db.status[b] = rc;
+        if (!db.many) return rc;
+        if (!first) first = rc;
     }
+    if (first) return first;
     HIP_OK(hipMemcpyAsync(xb.out_ptr, dstp.data(), 8 * (size_t)nblocks, hipMemcpyHostToDevice, st));
     HIP_OK(hipStreamSynchronize(st));
     hipLaunchKernelGGL(knz_copy_blocks_kernel, dim3(64, nblocks), dim3(256), 0, st, nblocks, xb.cur_ptr, xb.cur_len, xb.out_ptr, (const uint8_t*)nullptr);
@@ -729,11 +763,18 @@ static int dec_results(Handle* h, DecStage& d, hipStream_t st) {
     if (d.direct) HIP_OK(hipMemcpyAsync(db.pre_len.data(), h->blk_len.p, 4 * (size_t)nblocks, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     HIP_OK(hipGetLastError());
+    db.done = true;
+    int first = KNZ_OK;
     for (uint32_t b = 0; b < nblocks; b++) {
-        if (db.status[b]) return knz_set_error(h, db.status[b], db.status[b] == KNZ_ERR_CRC_CHECK ? "Corrupted bitstream: checksum mismatch" : "invalid entropy payload");
+        if (db.status[b]) {
+            const int rc = knz_set_error(h, db.status[b], db.status[b] == KNZ_ERR_CRC_CHECK ? "Corrupted bitstream: checksum mismatch" : "invalid entropy payload");
+            if (!db.many) return rc;
+            if (!first) first = rc;
+            continue;
+        }
         db.total_out += db.pre_len[b];
     }
-    return KNZ_OK;
+    return first;
 }
 
 static int decode_batch(Handle* h, DecodeBatch& db, hipStream_t st) {

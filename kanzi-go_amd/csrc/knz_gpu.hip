@@ -25,6 +25,7 @@
 #include "prims.h"
 #include "bwt_sort.hip"
 #include "layout.hip"
+#include "many.hip"
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -224,6 +225,7 @@ extern "C" int knz_close(void* handle) {
     if (h->own_stream) { hipStreamSynchronize(h->stream); hipStreamDestroy(h->stream); h->stream = nullptr; h->own_stream = false; }
     if (h->pinned) hipHostFree(h->pinned);
     if (h->pinned_rows) hipHostFree(h->pinned_rows);
+    if (h->many_pinned) hipHostFree(h->many_pinned);
     if (h->hstream && h->hstream != h->stream) { hipStreamSynchronize(h->hstream); hipStreamDestroy(h->hstream); }
     h->hstream = nullptr;
     for (int i = 0; i <= KNZ_STAGE_COUNT; i++) hipEventDestroy(h->ev[i]);
@@ -355,3 +357,4 @@ extern "C" int knz_dev_compress_blocks(void* handle, const void* d_src, uint64_t
 
 #include "knz_host_api.inc"
 #include "knz_multi.inc"
+#include "knz_many.inc"

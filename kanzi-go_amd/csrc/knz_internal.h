@@ -82,6 +82,9 @@ struct Handle {
     DevBuf a1_freqs, a1_tab, a1_ctxhdr, a1_ctxbits, a1_dtab, a1_info, a1_paybit, a1_f16, a1_ent, a1_cum, a1_ctxpos;
     DevBuf sa_keys0, sa_keys1, sa_vals0, sa_vals1, sa_rank, sa_gs, sa_head, sa_unres, sa_pos, sa_tmp, sa_links, sa_sp;
     DevBuf sa_hb, sa_tiles, sa_posl0, sa_posl1, sa_gid0, sa_gid1;   // suffix sort (bwt_sort.hip): head bits, per-tile tables, the large list
+    DevBuf many_tab, many_blk_stream, many_blk_pos, many_heads;     // several streams in one batch (many.hip): table of streams, owner and place of every block, the streams' heads
+    void* many_pinned = nullptr;      // ... the table of streams (and the heads) on the host: pinned, grow-only
+    size_t many_pinned_cap = 0;
     void* pinned = nullptr;           // small pinned host area for results
     // results of the last encode batch, one row per block + the batch totals behind them: packed on the device (knz_pack_results_kernel), ONE copy into pinned memory
     struct ResultRow { uint64_t written; uint64_t cksum; uint32_t post_len; int32_t status; uint32_t mode; uint32_t skip; };

@@ -1,0 +1,71 @@
+"""knz_dev_compress_many / knz_dev_decompress_many on the MI355X: every stream of a many call against the single calls of the same library
+and against the reference's Writer / Reader (oracle/_ref through tests/ref_lib.py); block sizes 1024, 16 KiB and 64 KiB."""
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def be():
+    import parity_cases as P
+    return P.GpuBackend()
+
+
+def test_many_coverage_guard_gpu():
+    import many_cases as M
+    M.check_coverage((1024, 1 << 14, 1 << 16))
+
+
+def test_many_api_gpu(be):
+    import many_cases as M
+    M.check_api(be)
+
+
+@pytest.mark.parametrize("bs", (1024, 1 << 14, 1 << 16))
+@pytest.mark.parametrize("pipe", range(7))
+def test_many_shapes_gpu(be, pipe, bs):
+    import many_cases as M
+    M.check_shapes(be, M.PIPELINES[pipe], bs)
+
+
+@pytest.mark.parametrize("k", (1, 2, 37))
+def test_many_k_gpu(be, k):
+    import many_cases as M
+    M.check_k(be, M.PIPELINES[k % 3], 1024, k)
+
+
+def test_many_group_limit_gpu(be):
+    import many_cases as M
+    M.check_group_limit(be)
+
+
+def test_many_one_batch_gpu(be):
+    import many_cases as M
+    M.check_one_batch(be)
+
+
+@pytest.mark.parametrize("pipe", (0, 2, 3))
+def test_many_mixed_trouble_gpu(be, pipe):
+    import many_cases as M
+    M.check_mixed_trouble(be, M.PIPELINES[pipe])
+
+
+@pytest.mark.parametrize("pipe", (0, 2))
+def test_many_small_destination_gpu(be, pipe):
+    import many_cases as M
+    M.check_small_destination(be, M.PIPELINES[pipe], sweep=pipe == 0)
+
+
+def test_many_short_inner_block_gpu(be):
+    import many_cases as M
+    M.check_short_inner(be)
+
+
+def test_many_lanes_gpu(be):
+    import many_cases as M
+    M.check_lanes(be)
+
+
+def test_many_alloc_split_gpu(be, monkeypatch):
+    import many_cases as M
+    M.check_alloc_split(be, monkeypatch)
