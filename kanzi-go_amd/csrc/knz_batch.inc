@@ -4,17 +4,29 @@
 
 // ---- encode batch ----------------------------------------------------------------------------------------------------
 // d_src: nblocks blocks, block b at b*block_size (last one shorter). Output either the framed .knz body/stream
-// (framed=1) or per-block local streams at out_stride bytes (framed=0).
+// (framed=1) or per-block local streams at out_stride bytes (framed=0). Made by one of the four named forms below.
 struct EncodeBatch {
     const uint8_t* d_src; uint64_t n;
     uint8_t* d_dst; uint64_t dst_cap;
-    int framed; int with_header; int with_end; int64_t header_input_size;
-    uint64_t out_stride;     // framed == 0
-    int payload_only;        // 1: single EntropyEncoder object, no block header bits
-    uint64_t total_bits;     // result
-    // several streams in one batch (knz_many.inc; framed == 0): the blocks are those of a table of streams, many_blocks of them, none longer than
-    // many_max_len; a block that fails leaves its status in blk_status for the caller instead of failing the batch
-    const ManyStream* many = nullptr; uint32_t many_streams = 0, many_blocks = 0, many_max_len = 0; uint32_t* many_blk_stream = nullptr;
+    int framed = 0, with_header = 0, with_end = 0; int64_t header_input_size = 0;
+    uint64_t out_stride = 0; // framed == 0
+    int payload_only = 0;    // 1: single EntropyEncoder object, no block header bits
+    uint64_t total_bits = 0; // result
+    // several streams in one batch (knz_many.inc; on block_streams): the blocks are those of a table of streams, `blocks` of them, none longer than
+    // max_len; a block that fails leaves its status in blk_status for the caller instead of failing the batch
+    struct Many { const ManyStream* streams = nullptr; uint32_t n_streams = 0, blocks = 0, max_len = 0; uint32_t* blk_stream = nullptr; } many;
+    // a whole .knz stream (header, framed blocks, end marker) ; a segment of one (framed blocks only) ; block-local streams, block b's at dst + b * stride
+    // (count of them, 64 bytes of slack behind the last) ; the bare payload of a single EntropyEncoder object (one block-local stream, no block header)
+    static EncodeBatch stream(const uint8_t* src, uint64_t n, uint8_t* dst, uint64_t cap, int64_t header_input_size) {
+        EncodeBatch eb = segment(src, n, dst, cap); eb.with_header = eb.with_end = 1; eb.header_input_size = header_input_size; return eb;
+    }
+    static EncodeBatch segment(const uint8_t* src, uint64_t n, uint8_t* dst, uint64_t cap) { EncodeBatch eb(src, n, dst, cap); eb.framed = 1; return eb; }
+    static EncodeBatch block_streams(const uint8_t* src, uint64_t n, uint8_t* dst, uint64_t stride, uint64_t count) {
+        EncodeBatch eb(src, n, dst, stride * count + 64); eb.out_stride = stride; return eb;
+    }
+    static EncodeBatch payload(const uint8_t* src, uint64_t n, uint8_t* dst, uint64_t cap) { EncodeBatch eb = block_streams(src, n, dst, cap, 1); eb.payload_only = 1; return eb; }
+private:
+    EncodeBatch(const uint8_t* src, uint64_t nn, uint8_t* dst, uint64_t cap) : d_src(src), n(nn), d_dst(dst), dst_cap(cap) {}
 };
 
 // ---- decode batch ---------------------------------------------------------------------------------------------------
@@ -39,6 +51,10 @@ struct DecodeBatch {
     DecodeBatch(const knz_cfg& c, const uint8_t* stream, uint64_t n, uint8_t* out, uint64_t cap)
         : d_stream(stream), nbytes(n), framed(1), first_bit(0), seg_bits(0), nblocks(0), d_out(out), out_cap(cap), out_stride(c.block_size),
           payload_only(0), given_len(0), entropy(c.entropy), checksum_bits(c.checksum_bits), block_size(c.block_size), transform(c.transform), total_out(0) {}
+    // ... staged payloads instead of a stream: n of them, their bit positions already on the device (dec_stage_payloads, many.hip), block b decoded to out + b * stride
+    void unframed(uint32_t n, uint64_t stride) { framed = 0; nblocks = n; out_stride = stride; }
+    // block b failed with rc: true = stop at this first one ; with `many` it is marked, `first` keeps the first code and the batch goes on
+    bool block_failed(uint32_t b, int rc, int& first) { status[b] = rc; if (!first) first = rc; return !many; }
 };
 
 // ---- entropy stage, encode side: one function per codec ----------------------------------------------------------------
@@ -397,19 +413,22 @@ struct EncTablesArgs {
     uint64_t* blk_off; uint32_t* blk_len; uint32_t* blk_src_len; uint8_t* blk_skip; uint8_t* blk_copy; int32_t* blk_status;
     uint8_t* active; uint8_t* side;
 };
-__global__ void knz_enc_tables_kernel(EncTablesArgs a) {
-    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= a.nblocks) return;
-    const uint64_t rest = a.n - (uint64_t)b * a.bs;
-    const uint32_t len = (uint32_t)(rest < a.bs ? rest : a.bs);
-    const bool copy = len <= 15 && !a.payload_only;
-    a.blk_off[b] = a.src + (uint64_t)b * a.bs;
+// row b of the tables: a block of len bytes at addr
+__device__ __forceinline__ void knz_enc_table_row(const EncTablesArgs& a, uint32_t b, uint64_t addr, uint32_t len, bool payload_only) {
+    const bool copy = len <= 15 && !payload_only;
+    a.blk_off[b] = addr;
     a.blk_len[b] = len;
-    a.blk_src_len[b] = a.payload_only ? (len > 16 ? len : 16u) : len;   // a bare EntropyEncoder has no copy-block rule
+    a.blk_src_len[b] = payload_only ? (len > 16 ? len : 16u) : len;     // a bare EntropyEncoder has no copy-block rule
     a.blk_copy[b] = copy ? 1 : 0;
     a.blk_skip[b] = (copy || a.none_only) ? 0x7F : 0xFF;                // NullTransform always applies: slot 0 cleared
     a.blk_status[b] = 0;
     if (a.active) { a.active[b] = (copy || a.none_only) ? 0 : 1; a.side[b] = 0; }
+}
+__global__ void knz_enc_tables_kernel(EncTablesArgs a) {
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= a.nblocks) return;
+    const uint64_t rest = a.n - (uint64_t)b * a.bs;
+    knz_enc_table_row(a, b, a.src + (uint64_t)b * a.bs, (uint32_t)(rest < a.bs ? rest : a.bs), a.payload_only != 0);
 }
 
 // ... of a batch over several streams: block b is block b - first_block of the stream that owns it
@@ -418,16 +437,8 @@ __global__ void knz_many_enc_tables_kernel(EncTablesArgs a, const ManyStream* s,
     if (b >= a.nblocks) return;
     const uint32_t k = knz_many_owner(s, K, b);
     const uint64_t at = (uint64_t)(b - s[k].first_block) * a.bs, rest = s[k].n - at;
-    const uint32_t len = (uint32_t)(rest < a.bs ? rest : a.bs);
-    const bool copy = len <= 15;
     blk_stream[b] = k;
-    a.blk_off[b] = s[k].src + at;
-    a.blk_len[b] = len;
-    a.blk_src_len[b] = len;
-    a.blk_copy[b] = copy ? 1 : 0;
-    a.blk_skip[b] = (copy || a.none_only) ? 0x7F : 0xFF;
-    a.blk_status[b] = 0;
-    if (a.active) { a.active[b] = (copy || a.none_only) ? 0 : 1; a.side[b] = 0; }
+    knz_enc_table_row(a, b, s[k].src + at, (uint32_t)(rest < a.bs ? rest : a.bs), false);
 }
 
 // the rows of Handle::ResultRow for the blocks of a batch, the totals (bits written, overflow flag) in the row behind the last block
@@ -452,9 +463,9 @@ static int encode_batch(Handle* h, EncodeBatch& eb, hipStream_t st) {
         return knz_set_error(h, KNZ_ERR_INVALID_CODEC, "transform/entropy combination has no device implementation in this build");
     const EntropyCodec& ec = *entropy_codec(cfg.entropy);
     const uint64_t bs = cfg.block_size;
-    const uint32_t nblocks = eb.many ? eb.many_blocks : (uint32_t)((eb.n + bs - 1) / bs);       // (0: Writer.Close on an empty stream, header + end marker only)
+    const uint32_t nblocks = eb.many.streams ? eb.many.blocks : (uint32_t)((eb.n + bs - 1) / bs);       // (0: Writer.Close on an empty stream, header + end marker only)
     const uint32_t chunkSize = ec.chunk;
-    const uint32_t maxPost = knz_max_encoded_len(cfg.transform, eb.many ? std::max<uint32_t>(eb.many_max_len, 1) : (uint32_t)std::min<uint64_t>(bs, eb.n ? eb.n : 1));
+    const uint32_t maxPost = knz_max_encoded_len(cfg.transform, eb.many.streams ? std::max<uint32_t>(eb.many.max_len, 1) : (uint32_t)std::min<uint64_t>(bs, eb.n ? eb.n : 1));
     const uint32_t cpb = std::max<uint32_t>(1, (maxPost + chunkSize - 1) / chunkSize);
     const size_t nslots = (size_t)std::max<uint32_t>(nblocks, 1) * cpb;
     const uint32_t slotStride = ec.slot_stride;
@@ -477,7 +488,7 @@ static int encode_batch(Handle* h, EncodeBatch& eb, hipStream_t st) {
         ta.blk_off = h->blk_off.as<uint64_t>(); ta.blk_len = h->blk_len.as<uint32_t>(); ta.blk_src_len = h->blk_src_len.as<uint32_t>();
         ta.blk_skip = h->blk_skip.as<uint8_t>(); ta.blk_copy = h->blk_copy.as<uint8_t>(); ta.blk_status = h->blk_status.as<int32_t>();
         ta.active = noneOnly ? nullptr : xb.active; ta.side = noneOnly ? nullptr : xb.side;
-        if (eb.many) hipLaunchKernelGGL(knz_many_enc_tables_kernel, dim3((nblocks + 255) / 256), dim3(256), 0, st, ta, eb.many, eb.many_streams, eb.many_blk_stream);
+        if (eb.many.streams) hipLaunchKernelGGL(knz_many_enc_tables_kernel, dim3((nblocks + 255) / 256), dim3(256), 0, st, ta, eb.many.streams, eb.many.n_streams, eb.many.blk_stream);
         else hipLaunchKernelGGL(knz_enc_tables_kernel, dim3((nblocks + 255) / 256), dim3(256), 0, st, ta);
     }
     const bool skipOpt = (cfg.flags & KNZ_FLAG_SKIP_BLOCKS) != 0 && !eb.payload_only && nblocks != 0;
@@ -559,18 +570,18 @@ static int encode_batch(Handle* h, EncodeBatch& eb, hipStream_t st) {
 
     // results come back packed: one row per block (bit count, checksum, post-transform length, status, mode, skip flags) and the batch totals, gathered
     // by one small kernel and brought over by ONE asynchronous copy into pinned memory, one synchronisation
-    if (h->res_rows.reserve(sizeof(Handle::ResultRow) * ((size_t)nblocks + 1)) || h->reserve_pinned_rows((size_t)nblocks))
+    if (h->res_rows.reserve(sizeof(Handle::ResultRow) * ((size_t)nblocks + 1)) || h->pinned_rows.reserve(sizeof(Handle::ResultRow) * ((size_t)nblocks + 1)))
         return knz_set_error(h, KNZ_ERR_CREATE_COMPRESSOR, "pinned host allocation failed");
     hipLaunchKernelGGL(knz_pack_results_kernel, dim3((nblocks + 1 + 255) / 256), dim3(256), 0, st, nblocks, (const uint64_t*)h->blk_written.as<uint64_t>(),
                        (const uint64_t*)h->blk_cksum.as<uint64_t>(), (const uint32_t*)h->blk_len.as<uint32_t>(), (const int32_t*)h->blk_status.as<int32_t>(),
                        (const uint32_t*)h->blk_hdr.as<uint32_t>(), (const uint8_t*)h->blk_skip.as<uint8_t>(), (const uint64_t*)h->total_bits.as<uint64_t>(),
                        h->res_rows.as<Handle::ResultRow>());
-    Handle::ResultRow* rows = h->pinned_rows;
+    Handle::ResultRow* rows = h->pinned_rows.as<Handle::ResultRow>();
     HIP_OK(hipMemcpyAsync(rows, h->res_rows.p, sizeof(Handle::ResultRow) * ((size_t)nblocks + 1), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     HIP_OK(hipGetLastError());
     if (rows[nblocks].cksum != 0) return knz_set_error(h, KNZ_ERR_WRITE_FILE, "destination buffer too small");     // (the totals row: bits, overflow flag)
-    for (uint32_t b = 0; b < nblocks && !eb.many; b++)
+    for (uint32_t b = 0; b < nblocks && !eb.many.streams; b++)
         if (rows[b].status != 0) return knz_set_error(h, rows[b].status, "block failed (the reference panics on this input: ERR_PROCESS_BLOCK)");
     eb.total_bits = rows[nblocks].written;
     h->post_bytes = 0;
@@ -686,10 +697,7 @@ static int dec_place_outputs(Handle* h, DecStage& d, hipStream_t st) {
         if (db.status[b]) rc = knz_set_error(h, db.status[b], "invalid block in stream");
         else if (xf) { if (db.pre_len[b] > xstride) rc = knz_set_error(h, KNZ_ERR_BLOCK_SIZE, "block larger than the decoder buffers"); }
         else rc = dec_block_fits(h, db, b);
-        if (!rc) continue;
-        db.status[b] = rc;
-        if (!db.many) return rc;
-        if (!first) first = rc;
+        if (rc && db.block_failed(b, rc, first)) return rc;
     }
     return first;
 }
@@ -731,10 +739,7 @@ static int dec_inverse_transforms(Handle* h, DecStage& d, hipStream_t st) {
     for (uint32_t b = 0; b < nblocks; b++) {
         rc = db.status[b] ? knz_set_error(h, db.status[b], "inverse transform failed") : dec_block_fits(h, db, b);
         dstp[b] = (uint64_t)db.d_out + (uint64_t)b * db.out_stride;
-        if (!rc) continue;
-        db.status[b] = rc;
-        if (!db.many) return rc;
-        if (!first) first = rc;
+        if (rc && db.block_failed(b, rc, first)) return rc;
     }
     if (first) return first;
     HIP_OK(hipMemcpyAsync(xb.out_ptr, dstp.data(), 8 * (size_t)nblocks, hipMemcpyHostToDevice, st));
@@ -768,11 +773,8 @@ static int dec_results(Handle* h, DecStage& d, hipStream_t st) {
     for (uint32_t b = 0; b < nblocks; b++) {
         if (db.status[b]) {
             const int rc = knz_set_error(h, db.status[b], db.status[b] == KNZ_ERR_CRC_CHECK ? "Corrupted bitstream: checksum mismatch" : "invalid entropy payload");
-            if (!db.many) return rc;
-            if (!first) first = rc;
-            continue;
-        }
-        db.total_out += db.pre_len[b];
+            if (db.block_failed(b, rc, first)) return rc;
+        } else db.total_out += db.pre_len[b];
     }
     return first;
 }

@@ -66,6 +66,10 @@ struct DeviceGuard {
     DeviceGuard& operator=(const DeviceGuard&) = delete;
 };
 
+// the stream a call runs on: the caller's or else the handle's own for device pointers ; the handle's non-blocking one, where it exists, for host pointers
+static hipStream_t dev_call_stream(const Handle* h, void* hip_stream) { return hip_stream ? (hipStream_t)hip_stream : h->stream; }
+static hipStream_t host_call_stream(const Handle* h) { return h->hstream ? h->hstream : h->stream; }
+
 // several lanes behind one handle (knz_multi.inc)
 static int multi_blocks(Handle* h, knz_block* blocks, int n, int job);
 static void multi_close(Handle* h);
@@ -224,8 +228,6 @@ extern "C" int knz_close(void* handle) {
     DeviceGuard dg(h);                                  // (the workspace buffers are freed by ~Handle while the device is bound)
     if (h->own_stream) { hipStreamSynchronize(h->stream); hipStreamDestroy(h->stream); h->stream = nullptr; h->own_stream = false; }
     if (h->pinned) hipHostFree(h->pinned);
-    if (h->pinned_rows) hipHostFree(h->pinned_rows);
-    if (h->many_pinned) hipHostFree(h->many_pinned);
     if (h->hstream && h->hstream != h->stream) { hipStreamSynchronize(h->hstream); hipStreamDestroy(h->hstream); }
     h->hstream = nullptr;
     for (int i = 0; i <= KNZ_STAGE_COUNT; i++) hipEventDestroy(h->ev[i]);
@@ -327,32 +329,26 @@ extern "C" uint32_t knz_max_encoded_len(uint64_t transform, uint32_t n) {     //
     return (uint32_t)std::min<uint64_t>(req, 0xFFFFFFFFu);
 }
 
+// the two device-resident encode calls: `out` takes the bytes of a whole stream, or the bits of a segment
+static int dev_encode(void* handle, EncodeBatch eb, uint64_t* out, bool bytes, void* hip_stream) {
+    Handle* h = lane_of_pointer((Handle*)handle, eb.d_dst);
+    if (!h || !eb.d_dst || !out || (!eb.d_src && eb.n)) return KNZ_ERR_MISSING_PARAM;
+    DeviceGuard dg(h);
+    if (((uintptr_t)eb.d_dst & 3) || ((uintptr_t)eb.d_src & 15)) return knz_set_error(h, KNZ_ERR_INVALID_PARAM, "d_src must be 16-byte and d_dst 4-byte aligned");
+    int rc = encode_batch(h, eb, dev_call_stream(h, hip_stream));
+    if (rc) return rc;
+    *out = bytes ? (eb.total_bits + 7) >> 3 : eb.total_bits;
+    return KNZ_OK;
+}
+
 extern "C" int knz_dev_compress(void* handle, const void* d_src, uint64_t n, int64_t header_input_size, void* d_dst,
                                 uint64_t dst_cap, uint64_t* out_bytes, void* hip_stream) {
-    Handle* h = lane_of_pointer((Handle*)handle, d_dst);
-    if (!h || !d_dst || !out_bytes || (!d_src && n)) return KNZ_ERR_MISSING_PARAM;
-    DeviceGuard dg(h);
-    if (((uintptr_t)d_dst & 3) || ((uintptr_t)d_src & 15)) return knz_set_error(h, KNZ_ERR_INVALID_PARAM, "d_src must be 16-byte and d_dst 4-byte aligned");
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : h->stream;
-    EncodeBatch eb{(const uint8_t*)d_src, n, (uint8_t*)d_dst, dst_cap, 1, 1, 1, header_input_size, 0, 0, 0};
-    int rc = encode_batch(h, eb, st);
-    if (rc) return rc;
-    *out_bytes = (eb.total_bits + 7) >> 3;
-    return KNZ_OK;
+    return dev_encode(handle, EncodeBatch::stream((const uint8_t*)d_src, n, (uint8_t*)d_dst, dst_cap, header_input_size), out_bytes, true, hip_stream);
 }
 
 extern "C" int knz_dev_compress_blocks(void* handle, const void* d_src, uint64_t n, void* d_dst, uint64_t dst_cap,
                                        uint64_t* out_bits, void* hip_stream) {
-    Handle* h = lane_of_pointer((Handle*)handle, d_dst);
-    if (!h || !d_dst || !out_bits || (!d_src && n)) return KNZ_ERR_MISSING_PARAM;
-    DeviceGuard dg(h);
-    if (((uintptr_t)d_dst & 3) || ((uintptr_t)d_src & 15)) return knz_set_error(h, KNZ_ERR_INVALID_PARAM, "d_src must be 16-byte and d_dst 4-byte aligned");
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : h->stream;
-    EncodeBatch eb{(const uint8_t*)d_src, n, (uint8_t*)d_dst, dst_cap, 1, 0, 0, 0, 0, 0, 0};
-    int rc = encode_batch(h, eb, st);
-    if (rc) return rc;
-    *out_bits = eb.total_bits;
-    return KNZ_OK;
+    return dev_encode(handle, EncodeBatch::segment((const uint8_t*)d_src, n, (uint8_t*)d_dst, dst_cap), out_bits, false, hip_stream);
 }
 
 #include "knz_host_api.inc"

@@ -44,7 +44,7 @@ extern "C" int knz_dev_decompress(void* handle, const void* d_src, uint64_t n_by
     if (!h || !d_src || !d_dst || !out_bytes) return KNZ_ERR_MISSING_PARAM;
     DeviceGuard dg(h);
     if ((uintptr_t)d_src & 3) return knz_set_error(h, KNZ_ERR_INVALID_PARAM, "d_src must be 4-byte aligned");
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : h->stream;
+    hipStream_t st = dev_call_stream(h, hip_stream);
     uint8_t hdr[32] = {0};
     HIP_OK(hipMemcpyAsync(hdr, d_src, std::min<uint64_t>(32, n_bytes), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
@@ -86,7 +86,7 @@ extern "C" int knz_dev_decompress_blocks(void* handle, const void* d_src, uint64
     if ((uintptr_t)d_src & 3) return knz_set_error(h, KNZ_ERR_INVALID_PARAM, "d_src must be 4-byte aligned");
     *out_bytes = 0;
     if (n_bits == 0) return KNZ_OK;
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : h->stream;
+    hipStream_t st = dev_call_stream(h, hip_stream);
     DecodeBatch db(h->cfg, (const uint8_t*)d_src, (n_bits + 7) >> 3, (uint8_t*)d_dst, dst_cap);
     db.seg_bits = n_bits;
     int rc = decode_batch(h, db, st);
@@ -98,20 +98,41 @@ extern "C" int knz_dev_decompress_blocks(void* handle, const void* d_src, uint64
 // ---- host-pointer batch entry points ------------------------------------------------------------------------------------
 static int encode_blocks_once(Handle* h, knz_block* blocks, int n);
 static int decode_blocks_once(Handle* h, knz_block* blocks, int n);
-// A batch whose workspace the device cannot hold any more (other handles, other tenants) is taken in halves after the handle's own workspace
-// has been given back: blocks are independent (Definitions.go:73-77), so the result is the same, with fewer of them side by side.
-template <typename F>
-static int blocks_split_retry(Handle* h, knz_block* blocks, int n, F once) {
+// A range [lo, lo + cnt) of blocks or streams whose workspace the device cannot hold any more (other handles, other tenants) is taken in halves after the
+// handle's own workspace has been given back: blocks are independent (Definitions.go:73-77), so the result is the same, with fewer of them side by side.
+// failed(lo, cnt, rc) hears of every range that failed for good ; both_halves: a first half that did still lets the second run ; callers: the caller's
+// stream or null, synchronised before the workspace goes (the handle's own ones always are).
+template <typename Once, typename Failed>
+static int split_retry(Handle* h, int lo, int cnt, bool both_halves, const hipStream_t* callers, Once once, Failed failed) {
     g_alloc_refused = false;
-    int rc = once(h, blocks, n);
-    if (rc == KNZ_OK || !g_alloc_refused) return rc;
-    knz_release_workspace(h);
-    g_alloc_refused = false;
-    if (n == 1) return once(h, blocks, n);                    // (once more with nothing else of this handle resident)
-    const int half = n / 2;
-    rc = blocks_split_retry(h, blocks, half, once);
-    if (rc) return rc;
-    return blocks_split_retry(h, blocks + half, n - half, once);
+    int rc = once(lo, cnt);
+    if (rc != KNZ_OK && g_alloc_refused) {
+        if (callers) hipStreamSynchronize(*callers);
+        knz_release_workspace(h);
+        g_alloc_refused = false;
+        if (cnt > 1) {
+            const int half = cnt / 2;
+            rc = split_retry(h, lo, half, both_halves, callers, once, failed);
+            if (rc && !both_halves) return rc;
+            const int rc2 = split_retry(h, lo + half, cnt - half, both_halves, callers, once, failed);
+            return rc ? rc : rc2;
+        }
+        rc = once(lo, cnt);                                       // (once more with nothing else of this handle resident)
+    }
+    if (rc != KNZ_OK) failed(lo, cnt, rc);
+    return rc;
+}
+// the blocks form: the first half that fails for good ends the batch with its code (knz_multi.inc's lanes call it for their ranges)
+static int blocks_split_retry(Handle* h, knz_block* blocks, int n, int (*once)(Handle*, knz_block*, int)) {
+    return split_retry(h, 0, n, false, nullptr, [&](int lo, int cnt) { return once(h, blocks + lo, cnt); }, [](int, int, int) {});
+}
+
+// What the block-local stream of a block of len bytes can take, rounded up to 64 (the stride of such streams in stage_out): the longest the transform
+// sequence can make the block, coded at 12 bits a byte at the worst (the longest Huffman code), 1 KiB for the block header and the coders' chunk
+// headers, and for rANS order 1 its context headers: up to 128 KiB per 4 MiB chunk, two chunks to spare.
+static uint64_t block_stream_bound(uint64_t transform, uint32_t entropy, uint64_t len) {
+    const uint64_t ans1 = entropy == KNZ_E_ANS1 ? 131072ull * (len / (4u << 20) + 2) : 0;
+    return ((uint64_t)knz_max_encoded_len(transform, (uint32_t)std::max<uint64_t>(len, 1)) * 12 / 8 + 1024 + ans1 + 63) & ~(uint64_t)63;
 }
 extern "C" int knz_encode_blocks(void* handle, knz_block* blocks, int n) {
     Handle* h = (Handle*)handle;
@@ -122,7 +143,7 @@ extern "C" int knz_encode_blocks(void* handle, knz_block* blocks, int n) {
     return blocks_split_retry(h, blocks, n, encode_blocks_once);
 }
 static int encode_blocks_once(Handle* h, knz_block* blocks, int n) {
-    hipStream_t st = h->hstream ? h->hstream : h->stream;
+    hipStream_t st = host_call_stream(h);
     const uint64_t bs = h->cfg.block_size;
     // stage the blocks at block_size stride; all but the last must be full for the shared block table
     for (int i = 0; i < n; i++) {
@@ -131,14 +152,14 @@ static int encode_blocks_once(Handle* h, knz_block* blocks, int n) {
         if (i + 1 < n && blocks[i].src_len != bs) return knz_set_error(h, KNZ_ERR_INVALID_PARAM, "only the last block of a batch may be short");
     }
     const uint64_t total = (uint64_t)(n - 1) * bs + blocks[n - 1].src_len;
-    const uint64_t ostride = ((uint64_t)knz_max_encoded_len(h->cfg.transform, (uint32_t)bs) * 12 / 8 + 1024 + (h->cfg.entropy == KNZ_E_ANS1 ? 131072ull * (bs / (4u << 20) + 2) : 0) + 63) & ~(uint64_t)63;
+    const uint64_t ostride = block_stream_bound(h->cfg.transform, h->cfg.entropy, bs);
     if (h->stage_in.reserve(total + 64) || h->stage_out.reserve(ostride * n + 64)) return knz_set_error(h, KNZ_ERR_CREATE_COMPRESSOR, "device workspace allocation failed");
     for (int i = 0; i < n; i++)
         HIP_OK(hipMemcpyAsync(h->stage_in.as<uint8_t>() + (uint64_t)i * bs, blocks[i].src, blocks[i].src_len, hipMemcpyHostToDevice, st));
-    EncodeBatch eb{h->stage_in.as<uint8_t>(), total, h->stage_out.as<uint8_t>(), ostride * n + 64, 0, 0, 0, 0, ostride, 0, 0};
+    EncodeBatch eb = EncodeBatch::block_streams(h->stage_in.as<uint8_t>(), total, h->stage_out.as<uint8_t>(), ostride, (uint64_t)n);
     int rc = encode_batch(h, eb, st);
     if (rc) { for (int i = 0; i < n; i++) blocks[i].status = rc; return rc; }
-    const Handle::ResultRow* rows = h->pinned_rows;   // (filled by encode_batch: nothing more to bring over but the streams themselves)
+    const Handle::ResultRow* rows = h->pinned_rows.as<Handle::ResultRow>();   // (filled by encode_batch: nothing more to bring over but the streams themselves)
     int worst = KNZ_OK;
     for (int i = 0; i < n; i++) {
         const uint64_t nb = (rows[i].written + 7) >> 3;
@@ -163,31 +184,41 @@ extern "C" int knz_decode_blocks(void* handle, knz_block* blocks, int n) {
     DeviceGuard dg(h);
     return blocks_split_retry(h, blocks, n, decode_blocks_once);
 }
-static int decode_blocks_once(Handle* h, knz_block* blocks, int n) {
-    hipStream_t st = h->hstream ? h->hstream : h->stream;
-    const uint64_t bs = h->cfg.block_size;
-    uint64_t total = 0;
+// Staging for an unframed decode: the payloads side by side in stage_in, each at a multiple of 8 bytes with zeros between and behind them, their bit
+// positions in blk_dst_bit and bit counts in blk_written, out_bytes of room in stage_out. `total`: the staged bytes.
+struct Payload { const uint8_t* p; uint64_t len; };
+static int dec_stage_payloads(Handle* h, const std::vector<Payload>& pl, uint64_t out_bytes, uint64_t& total, hipStream_t st) {
+    const size_t n = pl.size();
     std::vector<uint64_t> bit(n), bits(n);
+    total = 0;
+    for (size_t i = 0; i < n; i++) { bit[i] = total * 8; bits[i] = pl[i].len * 8; total += (pl[i].len + 7) & ~(uint64_t)7; }
+    if (h->stage_in.reserve(total + 64) || h->stage_out.reserve(out_bytes + 64) || h->blk_dst_bit.reserve(8 * n + 8) || h->blk_written.reserve(8 * n + 8))
+        return knz_set_error(h, KNZ_ERR_CREATE_DECOMPRESSOR, "device workspace allocation failed");
+    HIP_OK(hipMemsetAsync(h->stage_in.p, 0, total + 64, st));
+    for (size_t i = 0; i < n; i++)
+        HIP_OK(hipMemcpyAsync(h->stage_in.as<uint8_t>() + (bit[i] >> 3), pl[i].p, pl[i].len, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(h->blk_dst_bit.p, bit.data(), 8 * n, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(h->blk_written.p, bits.data(), 8 * n, hipMemcpyHostToDevice, st));
+    HIP_OK(hipStreamSynchronize(st));
+    return KNZ_OK;
+}
+
+static int decode_blocks_once(Handle* h, knz_block* blocks, int n) {
+    hipStream_t st = host_call_stream(h);
+    const uint64_t bs = h->cfg.block_size;
+    std::vector<Payload> pl(n);
     for (int i = 0; i < n; i++) {
         blocks[i].status = 0;
         if (!blocks[i].src || !blocks[i].dst || blocks[i].src_len == 0) return knz_set_error(h, KNZ_ERR_INVALID_PARAM, "invalid block descriptor");
-        bit[i] = total * 8;
-        bits[i] = (uint64_t)blocks[i].src_len * 8;
-        total += ((uint64_t)blocks[i].src_len + 7) & ~(uint64_t)7;
+        pl[i] = {blocks[i].src, blocks[i].src_len};
     }
     const uint64_t ostride = (bs + 63) & ~(uint64_t)63;
-    if (h->stage_in.reserve(total + 64) || h->stage_out.reserve(ostride * n + 64) || h->blk_dst_bit.reserve(8 * (size_t)n + 8) ||
-        h->blk_written.reserve(8 * (size_t)n + 8))
-        return knz_set_error(h, KNZ_ERR_CREATE_DECOMPRESSOR, "device workspace allocation failed");
-    HIP_OK(hipMemsetAsync(h->stage_in.p, 0, total + 64, st));
-    for (int i = 0; i < n; i++)
-        HIP_OK(hipMemcpyAsync(h->stage_in.as<uint8_t>() + (bit[i] >> 3), blocks[i].src, blocks[i].src_len, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(h->blk_dst_bit.p, bit.data(), 8 * (size_t)n, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(h->blk_written.p, bits.data(), 8 * (size_t)n, hipMemcpyHostToDevice, st));
-    HIP_OK(hipStreamSynchronize(st));
+    uint64_t total = 0;
+    int rc = dec_stage_payloads(h, pl, ostride * n, total, st);
+    if (rc) return rc;
     DecodeBatch db(h->cfg, h->stage_in.as<uint8_t>(), total, h->stage_out.as<uint8_t>(), ostride * n);
-    db.framed = 0; db.nblocks = (uint32_t)n; db.out_stride = ostride;
-    int rc = decode_batch(h, db, st);
+    db.unframed((uint32_t)n, ostride);
+    rc = decode_batch(h, db, st);
     if (rc) {
         for (int i = 0; i < n; i++) blocks[i].status = (i < (int)db.status.size() && db.status[i]) ? db.status[i] : rc;
         return rc;
@@ -234,7 +265,7 @@ extern "C" int knz_dev_assemble(void* handle, int64_t header_input_size, const v
     if (!h || !d_dst || !out_bytes || (n_segments && (!d_segments || !segment_bits))) return KNZ_ERR_MISSING_PARAM;
     DeviceGuard dg(h);
     if ((uintptr_t)d_dst & 3) return knz_set_error(h, KNZ_ERR_INVALID_PARAM, "d_dst must be 4-byte aligned");
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : h->stream;
+    hipStream_t st = dev_call_stream(h, hip_stream);
     uint32_t words[8];
     const uint32_t hbits = knz_build_stream_header(h->cfg, header_input_size, words);
     uint64_t total = hbits;
@@ -280,7 +311,10 @@ extern "C" int knz_dev_assemble(void* handle, int64_t header_input_size, const v
 
 // ---- single kanzi.ByteTransform / EntropyEncoder / EntropyDecoder objects ------------------------------------------------
 // One ByteTransform object on one buffer: a batch of one block through the same stage kernels.
-static int transform_single(Handle* h, uint64_t type1, bool forward, const uint8_t* src, uint32_t n, uint8_t* dst, uint32_t cap, uint32_t* out_n) {
+static int transform_single(void* handle, uint64_t type1, bool forward, const uint8_t* src, uint32_t n, uint8_t* dst, uint32_t cap, uint32_t* out_n) {
+    Handle* h = lane0((Handle*)handle);
+    if (!h || !src || !dst || !out_n) return KNZ_ERR_MISSING_PARAM;
+    DeviceGuard dg(h);
     if (!xf_codec((uint32_t)type1)) return knz_set_error(h, KNZ_ERR_INVALID_CODEC, "transform has no device implementation in this build");
     *out_n = 0;
     if (n == 0 || cap == 0) return KNZ_OK;                                  // every Forward/Inverse returns (0,0,nil) on empty input
@@ -290,7 +324,7 @@ static int transform_single(Handle* h, uint64_t type1, bool forward, const uint8
         *out_n = n;
         return KNZ_OK;
     }
-    hipStream_t st = h->hstream ? h->hstream : h->stream;
+    hipStream_t st = host_call_stream(h);
     XfBatch x;
     const uint64_t stride = ((uint64_t)cap + 15) & ~(uint64_t)15;
     if (xf_alloc(h, x, 1, stride) || h->stage_in.reserve((uint64_t)n + 64) || h->blk_off.reserve(16) || h->blk_len.reserve(16) ||
@@ -333,17 +367,11 @@ static int transform_single(Handle* h, uint64_t type1, bool forward, const uint8
 }
 
 extern "C" int knz_transform_forward(void* handle, uint64_t type1, const uint8_t* src, uint32_t n, uint8_t* dst, uint32_t cap, uint32_t* out_n) {
-    Handle* h = lane0((Handle*)handle);
-    if (!h || !src || !dst || !out_n) return KNZ_ERR_MISSING_PARAM;
-    DeviceGuard dg(h);
-    return transform_single(h, type1, true, src, n, dst, cap, out_n);
+    return transform_single(handle, type1, true, src, n, dst, cap, out_n);
 }
 
 extern "C" int knz_transform_inverse(void* handle, uint64_t type1, const uint8_t* src, uint32_t n, uint8_t* dst, uint32_t cap, uint32_t* out_n) {
-    Handle* h = lane0((Handle*)handle);
-    if (!h || !src || !dst || !out_n) return KNZ_ERR_MISSING_PARAM;
-    DeviceGuard dg(h);
-    return transform_single(h, type1, false, src, n, dst, cap, out_n);
+    return transform_single(handle, type1, false, src, n, dst, cap, out_n);
 }
 
 extern "C" int knz_entropy_encode(void* handle, uint32_t type, const uint8_t* src, uint32_t n, uint8_t* bits, uint64_t cap_bytes, uint64_t* out_bits) {
@@ -354,7 +382,7 @@ extern "C" int knz_entropy_encode(void* handle, uint32_t type, const uint8_t* sr
     *out_bits = 0;
     if (n == 0) return KNZ_OK;                 // HuffmanEncoder.Write(len 0) writes nothing (:395-397)
     if (n > (1u << 30)) return knz_set_error(h, KNZ_ERR_BLOCK_SIZE, "Invalid block size parameter (max is 1<<30)");   // FPAQCodec.go:128-130 and friends
-    hipStream_t st = h->hstream ? h->hstream : h->stream;
+    hipStream_t st = host_call_stream(h);
     knz_cfg saved = h->cfg;
     h->cfg.entropy = type; h->cfg.transform = 0; h->cfg.checksum_bits = 0;
     h->cfg.block_size = std::max<uint32_t>(1024, (n + 15) & ~15u);
@@ -364,9 +392,9 @@ extern "C" int knz_entropy_encode(void* handle, uint32_t type, const uint8_t* sr
     uint64_t written = 0;
     if (!rc) {
         hipMemcpyAsync(h->stage_in.p, src, n, hipMemcpyHostToDevice, st);
-        EncodeBatch eb{h->stage_in.as<uint8_t>(), n, h->stage_out.as<uint8_t>(), ocap + 64, 0, 0, 0, 0, ocap, 1, 0};
+        EncodeBatch eb = EncodeBatch::payload(h->stage_in.as<uint8_t>(), n, h->stage_out.as<uint8_t>(), ocap);
         rc = encode_batch(h, eb, st);
-        if (!rc) written = h->pinned_rows[0].written;       // (the batch's result rows are on the host already)
+        if (!rc) written = h->pinned_rows.as<Handle::ResultRow>()[0].written;       // (the batch's result rows are on the host already)
     }
     h->cfg = saved;
     if (rc) return rc;
@@ -385,21 +413,15 @@ extern "C" int knz_entropy_decode(void* handle, uint32_t type, const uint8_t* bi
     if (!entropy_on_device(type)) return knz_set_error(h, KNZ_ERR_INVALID_CODEC, "entropy codec has no device implementation in this build");
     if (used_bits) *used_bits = 0;
     if (n == 0) return KNZ_OK;
-    hipStream_t st = h->hstream ? h->hstream : h->stream;
-    const uint64_t padded = (n_bytes + 7) & ~(uint64_t)7;
-    if (h->stage_in.reserve(padded + 64) || h->stage_out.reserve((uint64_t)n + 64) || h->blk_dst_bit.reserve(16) || h->blk_written.reserve(16))
-        return knz_set_error(h, KNZ_ERR_CREATE_DECOMPRESSOR, "device workspace allocation failed");
-    HIP_OK(hipMemsetAsync(h->stage_in.p, 0, padded + 64, st));
-    HIP_OK(hipMemcpyAsync(h->stage_in.p, bits, n_bytes, hipMemcpyHostToDevice, st));
-    uint64_t zero = 0, nb = n_bytes * 8;
-    HIP_OK(hipMemcpyAsync(h->blk_dst_bit.p, &zero, 8, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(h->blk_written.p, &nb, 8, hipMemcpyHostToDevice, st));
-    HIP_OK(hipStreamSynchronize(st));
+    hipStream_t st = host_call_stream(h);
+    uint64_t padded = 0;
+    int rc = dec_stage_payloads(h, {Payload{bits, n_bytes}}, n, padded, st);
+    if (rc) return rc;
     knz_cfg oc = h->cfg;                                   // a bare EntropyDecoder: one payload of n bytes, no block header, no transform, no checksum
     oc.entropy = type; oc.transform = 0; oc.checksum_bits = 0; oc.block_size = std::max<uint32_t>(1024, n);
     DecodeBatch db(oc, h->stage_in.as<uint8_t>(), padded, h->stage_out.as<uint8_t>(), n);
-    db.framed = 0; db.nblocks = 1; db.out_stride = n; db.payload_only = 1; db.given_len = n;
-    int rc = decode_batch(h, db, st);
+    db.unframed(1, n); db.payload_only = 1; db.given_len = n;
+    rc = decode_batch(h, db, st);
     if (rc) return rc;
     HIP_OK(hipMemcpyAsync(dst, h->stage_out.p, n, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));

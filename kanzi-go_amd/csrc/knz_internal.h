@@ -29,6 +29,24 @@ struct DevBuf {
     template <typename T> T* as() const { return (T*)p; }
 };
 
+// Pinned host memory a batch's tables go up from and its results come back into, one copy each. Grows (never shrinks); contents are not preserved.
+struct PinnedBuf {
+    void* p = nullptr; size_t cap = 0;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf&) = delete; PinnedBuf& operator=(const PinnedBuf&) = delete;
+    ~PinnedBuf() { if (p) hipHostFree(p); }       // with the Handle (knz_close deletes it while its device is bound)
+    int reserve(size_t n) {
+        if (n <= cap) return 0;
+        if (p) hipHostFree(p);
+        p = nullptr; cap = 0;
+        const size_t want = n + n / 4 + 4096;
+        if (hipHostMalloc(&p, want) != hipSuccess) { (void)hipGetLastError(); return -1; }
+        cap = want;
+        return 0;
+    }
+    template <typename T> T* as() const { return (T*)p; }
+};
+
 // HIP-event pair around one launch of a kernel that can dominate a batch (bench.py's roofline line reads these)
 #define KNZ_MAX_PROBES 128
 struct KernelProbe { const char* name = nullptr; hipEvent_t a = nullptr, b = nullptr; };
@@ -83,23 +101,12 @@ struct Handle {
     DevBuf sa_keys0, sa_keys1, sa_vals0, sa_vals1, sa_rank, sa_gs, sa_head, sa_unres, sa_pos, sa_tmp, sa_links, sa_sp;
     DevBuf sa_hb, sa_tiles, sa_posl0, sa_posl1, sa_gid0, sa_gid1;   // suffix sort (bwt_sort.hip): head bits, per-tile tables, the large list
     DevBuf many_tab, many_blk_stream, many_blk_pos, many_heads;     // several streams in one batch (many.hip): table of streams, owner and place of every block, the streams' heads
-    void* many_pinned = nullptr;      // ... the table of streams (and the heads) on the host: pinned, grow-only
-    size_t many_pinned_cap = 0;
+    PinnedBuf many_pinned;            // ... the table of streams (and the heads) on the host
     void* pinned = nullptr;           // small pinned host area for results
     // results of the last encode batch, one row per block + the batch totals behind them: packed on the device (knz_pack_results_kernel), ONE copy into pinned memory
     struct ResultRow { uint64_t written; uint64_t cksum; uint32_t post_len; int32_t status; uint32_t mode; uint32_t skip; };
     DevBuf res_rows;
-    ResultRow* pinned_rows = nullptr; // grow-only
-    size_t pinned_rows_cap = 0;
-    int reserve_pinned_rows(size_t n) {
-        if (n + 1 <= pinned_rows_cap) return 0;
-        if (pinned_rows) hipHostFree(pinned_rows);
-        pinned_rows = nullptr; pinned_rows_cap = 0;
-        const size_t want = n + n / 4 + 64;
-        if (hipHostMalloc((void**)&pinned_rows, sizeof(ResultRow) * want) != hipSuccess) return -1;
-        pinned_rows_cap = want;
-        return 0;
-    }
+    PinnedBuf pinned_rows;            // ... on the host
     std::vector<DevBuf*> all_bufs;    // every workspace buffer of this handle (filled while the handle is constructed)
     hipEvent_t ev[KNZ_STAGE_COUNT + 1];
     bool ev_valid = false;

@@ -3,35 +3,11 @@
 // over a block table the device derives from the table of streams; many.hip assembles the K streams (encode) or places the decoded blocks
 // (decode). Launches and copies do not grow with K: the table of streams goes up and comes back as one pinned copy each.
 
-static int many_reserve_pinned(Handle* h, size_t bytes) {
-    if (bytes <= h->many_pinned_cap) return 0;
-    if (h->many_pinned) hipHostFree(h->many_pinned);
-    h->many_pinned = nullptr; h->many_pinned_cap = 0;
-    const size_t want = bytes + bytes / 4 + 4096;
-    if (hipHostMalloc(&h->many_pinned, want) != hipSuccess) { (void)hipGetLastError(); return -1; }
-    h->many_pinned_cap = want;
-    return 0;
-}
-
-// A range of streams whose workspace the device refuses is taken in halves after the handle's workspace has been given back (blocks_split_retry's
-// rule, for streams). once(lo, cnt) returns 0 with every stream's result set, or a code with none of them touched: what fails for good marks its range.
+// split_retry's streams form: once(lo, cnt) returns 0 with every stream's result set, or a code with none of them touched. Both halves of a range run,
+// what fails for good marks its range, and the caller's stream has run dry before the workspace goes.
 template <typename F>
-static void many_split_retry(Handle* h, knz_stream* s, int lo, int cnt, hipStream_t st, F once) {
-    g_alloc_refused = false;
-    int rc = once(lo, cnt);
-    if (rc != KNZ_OK && g_alloc_refused) {
-        hipStreamSynchronize(st);
-        knz_release_workspace(h);
-        g_alloc_refused = false;
-        if (cnt > 1) {
-            const int half = cnt / 2;
-            many_split_retry(h, s, lo, half, st, once);
-            many_split_retry(h, s, lo + half, cnt - half, st, once);
-            return;
-        }
-        rc = once(lo, cnt);                                               // (once more with nothing else of this handle resident)
-    }
-    if (rc != KNZ_OK) for (int k = lo; k < lo + cnt; k++) if (s[k].status == 0) s[k].status = rc;
+static void many_split_retry(Handle* h, knz_stream* s, int n, hipStream_t st, F once) {
+    split_retry(h, 0, n, true, &st, once, [&](int lo, int cnt, int rc) { for (int k = lo; k < lo + cnt; k++) if (s[k].status == 0) s[k].status = rc; });
 }
 
 // the lane a call runs on (the one that owns streams[0].d_dst) and, per stream, what can be refused before the device is asked
@@ -63,8 +39,8 @@ static unsigned many_copy_y(uint64_t stride) { return (unsigned)std::min<uint64_
 static int compress_many_once(Handle* h, knz_stream* s, int n, hipStream_t st) {
     const knz_cfg& cfg = h->cfg;
     const uint64_t bs = cfg.block_size;
-    if (many_reserve_pinned(h, sizeof(ManyStream) * (size_t)n)) return knz_set_error(h, KNZ_ERR_CREATE_COMPRESSOR, "pinned host allocation failed");
-    ManyStream* tab = (ManyStream*)h->many_pinned;
+    if (h->many_pinned.reserve(sizeof(ManyStream) * (size_t)n)) return knz_set_error(h, KNZ_ERR_CREATE_COMPRESSOR, "pinned host allocation failed");
+    ManyStream* tab = h->many_pinned.as<ManyStream>();
     uint64_t nblocks = 0, maxLen = 0;
     for (int k = 0; k < n; k++) {
         ManyStream& m = tab[k];
@@ -76,18 +52,16 @@ static int compress_many_once(Handle* h, knz_stream* s, int n, hipStream_t st) {
         maxLen = std::max(maxLen, std::min<uint64_t>(m.n, bs));
     }
     if (nblocks >= (1u << 30)) return knz_set_error(h, KNZ_ERR_BLOCK_SIZE, "too many blocks in one call");
-    // block-local streams at a fixed stride (knz_encode_blocks' bound), sized by the longest block of the call, not by the block size
-    const uint64_t ostride = ((uint64_t)knz_max_encoded_len(cfg.transform, (uint32_t)std::max<uint64_t>(maxLen, 1)) * 12 / 8 + 1024 +
-                              (cfg.entropy == KNZ_E_ANS1 ? 131072ull * (maxLen / (4u << 20) + 2) : 0) + 63) & ~(uint64_t)63;
+    // block-local streams at a fixed stride, sized by the longest block of the call, not by the block size
+    const uint64_t ostride = block_stream_bound(cfg.transform, cfg.entropy, maxLen);
     if (h->many_tab.reserve(sizeof(ManyStream) * (size_t)n) || h->many_blk_stream.reserve(4 * (nblocks + 1)) || h->many_blk_pos.reserve(8 * (nblocks + 1)) ||
         h->stage_out.reserve(ostride * nblocks + 64) || h->total_bits.reserve(64))
         return knz_set_error(h, KNZ_ERR_CREATE_COMPRESSOR, "device workspace allocation failed");
     ManyStream* dtab = h->many_tab.as<ManyStream>();
     HIP_OK(hipMemcpyAsync(dtab, tab, sizeof(ManyStream) * (size_t)n, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(knz_many_scan_kernel, dim3(1), dim3(256), 0, st, dtab, (uint32_t)n, bs, 1u, h->total_bits.as<uint32_t>() + 8);
-    EncodeBatch eb{nullptr, 0, h->stage_out.as<uint8_t>(), ostride * nblocks + 64, 0, 0, 0, 0, ostride, 0, 0};
-    eb.many = dtab; eb.many_streams = (uint32_t)n; eb.many_blocks = (uint32_t)nblocks; eb.many_max_len = (uint32_t)maxLen;
-    eb.many_blk_stream = h->many_blk_stream.as<uint32_t>();
+    EncodeBatch eb = EncodeBatch::block_streams(nullptr, 0, h->stage_out.as<uint8_t>(), ostride, nblocks);
+    eb.many = {dtab, (uint32_t)n, (uint32_t)nblocks, (uint32_t)maxLen, h->many_blk_stream.as<uint32_t>()};
     int rc = encode_batch(h, eb, st);
     if (rc) return rc;
     ManyAsmArgs a;
@@ -107,13 +81,10 @@ extern "C" int knz_dev_compress_many(void* handle, knz_stream* streams, int n, v
     if (n <= 0) return KNZ_OK;
     Handle* h = many_begin(handle, streams, n, true);
     DeviceGuard dg(h);
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : h->stream;
-    many_split_retry(h, streams, 0, n, st, [&](int lo, int cnt) { return compress_many_once(h, streams + lo, cnt, st); });
+    hipStream_t st = dev_call_stream(h, hip_stream);
+    many_split_retry(h, streams, n, st, [&](int lo, int cnt) { return compress_many_once(h, streams + lo, cnt, st); });
     return many_end(h, streams, n);
 }
-
-// what the host parsed of every stream's header before the batch: the call's codec parameters (the first stream's) and every first block's bit
-struct ManyHeads { knz_cfg sc; std::vector<uint32_t> first_bit; };
 
 static int decompress_many_once(Handle* h, knz_stream* s, const uint32_t* firstBit, const knz_cfg& sc, int n, hipStream_t st) {
     std::vector<int> active;
@@ -123,8 +94,8 @@ static int decompress_many_once(Handle* h, knz_stream* s, const uint32_t* firstB
     const uint64_t ostride = ((uint64_t)sc.block_size + 63) & ~(uint64_t)63;
     while (!active.empty()) {
         const int A = (int)active.size();
-        if (many_reserve_pinned(h, sizeof(ManyStream) * (size_t)A)) return knz_set_error(h, KNZ_ERR_CREATE_DECOMPRESSOR, "pinned host allocation failed");
-        ManyStream* tab = (ManyStream*)h->many_pinned;
+        if (h->many_pinned.reserve(sizeof(ManyStream) * (size_t)A)) return knz_set_error(h, KNZ_ERR_CREATE_DECOMPRESSOR, "pinned host allocation failed");
+        ManyStream* tab = h->many_pinned.as<ManyStream>();
         uint64_t staged = 0;
         for (int i = 0; i < A; i++) {
             const knz_stream& c = s[active[i]];
@@ -156,7 +127,7 @@ static int decompress_many_once(Handle* h, knz_stream* s, const uint32_t* firstB
         w.fill = 1; w.blk_bit = h->blk_dst_bit.as<uint64_t>(); w.blk_bits = h->blk_written.as<uint64_t>(); w.blk_stream = h->many_blk_stream.as<uint32_t>();
         hipLaunchKernelGGL(knz_many_walk_kernel, dim3((A + 63) / 64), dim3(64), 0, st, w);
         DecodeBatch db(sc, h->stage_in.as<uint8_t>(), staged, h->stage_out.as<uint8_t>(), ostride * nblocks);
-        db.framed = 0; db.nblocks = (uint32_t)nblocks; db.out_stride = ostride; db.many = true;
+        db.unframed((uint32_t)nblocks, ostride); db.many = true;
         const int rc = decode_batch(h, db, st);
         if (rc && !db.done) {
             // a block was refused before the batch had run to its end: its stream takes the code and leaves, the others go through again
@@ -193,15 +164,15 @@ extern "C" int knz_dev_decompress_many(void* handle, knz_stream* streams, int n,
     if (n <= 0) return KNZ_OK;
     Handle* h = many_begin(handle, streams, n, false);
     DeviceGuard dg(h);
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : h->stream;
+    hipStream_t st = dev_call_stream(h, hip_stream);
     // every stream's head: one device-side gather, one copy into pinned memory; the headers are parsed here as knz_dev_decompress parses one
     const size_t tabBytes = sizeof(ManyStream) * (size_t)n;
-    if (many_reserve_pinned(h, tabBytes + 32 * (size_t)n) || h->many_tab.reserve(tabBytes) || h->many_heads.reserve(32 * (size_t)n)) {
+    if (h->many_pinned.reserve(tabBytes + 32 * (size_t)n) || h->many_tab.reserve(tabBytes) || h->many_heads.reserve(32 * (size_t)n)) {
         for (int k = 0; k < n; k++) if (!streams[k].status) streams[k].status = KNZ_ERR_CREATE_DECOMPRESSOR;
         return many_end(h, streams, n);
     }
-    ManyStream* tab = (ManyStream*)h->many_pinned;
-    uint8_t* heads = (uint8_t*)h->many_pinned + tabBytes;
+    ManyStream* tab = h->many_pinned.as<ManyStream>();
+    uint8_t* heads = h->many_pinned.as<uint8_t>() + tabBytes;
     for (int k = 0; k < n; k++) {
         memset(&tab[k], 0, sizeof(ManyStream));
         tab[k].src = (uint64_t)streams[k].d_src; tab[k].n = streams[k].n; tab[k].status = streams[k].status;
@@ -210,20 +181,20 @@ extern "C" int knz_dev_decompress_many(void* handle, knz_stream* streams, int n,
     hipLaunchKernelGGL(knz_many_heads_kernel, dim3((n * 8 + 255) / 256), dim3(256), 0, st, (const ManyStream*)h->many_tab.as<ManyStream>(), (uint32_t)n, h->many_heads.as<uint32_t>());
     HIP_OK(hipMemcpyAsync(heads, h->many_heads.p, 32 * (size_t)n, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
-    ManyHeads mh;
-    mh.first_bit.assign(n, 0);
+    knz_cfg msc = h->cfg;                                                 // the call's codec parameters (the first stream's) and every first block's bit
+    std::vector<uint32_t> firstBit(n, 0);
     bool have = false;
     for (int k = 0; k < n; k++) {
         if (streams[k].status) continue;
         knz_cfg sc = h->cfg;
         int64_t outputSize = 0;
-        const int rc = parse_stream_header(h, heads + 32 * (size_t)k, streams[k].n, sc, outputSize, mh.first_bit[k]);
+        const int rc = parse_stream_header(h, heads + 32 * (size_t)k, streams[k].n, sc, outputSize, firstBit[k]);
         if (rc) { streams[k].status = rc; continue; }
-        if (!have) { mh.sc = sc; have = true; continue; }
-        if (sc.transform != mh.sc.transform || sc.entropy != mh.sc.entropy || sc.block_size != mh.sc.block_size || sc.checksum_bits != mh.sc.checksum_bits)
+        if (!have) { msc = sc; have = true; continue; }
+        if (sc.transform != msc.transform || sc.entropy != msc.entropy || sc.block_size != msc.block_size || sc.checksum_bits != msc.checksum_bits)
             streams[k].status = KNZ_ERR_INVALID_PARAM;                    // one batch, one set of codec parameters: the first stream's
     }
     if (have)
-        many_split_retry(h, streams, 0, n, st, [&](int lo, int cnt) { return decompress_many_once(h, streams + lo, mh.first_bit.data() + lo, mh.sc, cnt, st); });
+        many_split_retry(h, streams, n, st, [&](int lo, int cnt) { return decompress_many_once(h, streams + lo, firstBit.data() + lo, msc, cnt, st); });
     return many_end(h, streams, n);
 }

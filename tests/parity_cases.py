@@ -1618,3 +1618,192 @@ def check_corrupt_streams(be, trials=12):
             if exp is not None:
                 assert got == exp, (transform, entropy, t)
         c.close()
+
+
+def check_entry_contract(be):
+    """What the C entry points answer to bad arguments, asked through ctypes on the library itself (Codec filters some of these): the return code
+    and, where a handle exists, the text knz_last_error gives afterwards. A call that is refused without a text leaves the handle's last text as it
+    was; a call on a lane of a knz_open_devices handle leaves its text on the lane, so the handle's own stays as it was too. Block size 1024,
+    transform NONE, entropy HUFFMAN, at most 3000 bytes: every refused call is refused on the host, the others are ordinary small batches."""
+    import ctypes as C
+    Block, Stream = K.api._Block, K.api._Stream
+    MISSING, CODEC, WRITE, PROCESS, FILE, VERSION, PARAM, SKIP = 1, 3, 12, 13, 15, 16, 18, -1
+    bs, tt, et = 1024, O.transform_type("NONE"), O.entropy_type("HUFFMAN")
+    data = corpus(3000, 31)
+    parts = [data[:bs], data[bs:2 * bs], data[2 * bs:]]
+    one = K.Codec("NONE", "HUFFMAN", bs, lib=be.lib)
+    two = K.Codec("NONE", "HUFFMAN", bs, lib=be.lib, devices=[0, 0])
+    L = one.L
+    u8p = C.POINTER(C.c_uint8)
+
+    def text(h):
+        return L.knz_last_error(h).decode()
+
+    def expect(h, want_rc, want_text, fn, *args):
+        """want_text None: the call sets no text (the handle's last one stays)"""
+        before = text(h) if h else None
+        rc = fn(h, *args)
+        assert rc == want_rc, (fn.__name__, rc, want_rc)
+        if h:
+            assert text(h) == (before if want_text is None else want_text), (fn.__name__, text(h), want_text)
+
+    def host(b):
+        a = np.frombuffer(bytes(b), dtype=np.uint8).copy()
+        return a, a.ctypes.data_as(u8p)
+
+    def block_array(srcs, caps):
+        arr, keep = (Block * len(srcs))(), []
+        for i, (s, cap) in enumerate(zip(srcs, caps)):
+            a, o = np.frombuffer(bytes(s), dtype=np.uint8).copy(), np.zeros(max(cap, 16), dtype=np.uint8)
+            keep.append((a, o))
+            arr[i].src, arr[i].src_len, arr[i].dst, arr[i].dst_cap = a.ctypes.data, len(a), o.ctypes.data, cap
+        return arr, keep
+
+    cap = 2 * len(data) + 262144
+    src, ksrc = be.to_dev(data)
+    dst, kdst = be.empty(cap)
+    back, kback = be.empty(len(data) + 64)
+    good = O.compress(data, "NONE", "HUFFMAN", bs)
+    sp, ksp = be.to_dev(good, 4)
+    out = C.c_uint64()
+    o = C.byref(out)
+    n32 = C.c_uint32()
+    hbuf, hp = host(data[:500])
+    obuf, op = host(bytes(4096))
+
+    # ---- a null handle, on every entry point ----
+    arr, keep = block_array(parts, [4096] * 3)
+    st1 = (Stream * 1)()
+    st1[0].d_src, st1[0].n, st1[0].d_dst, st1[0].dst_cap = src, len(data), dst, cap
+    segs1, bits1 = (C.c_void_p * 1)(dst), (C.c_uint64 * 1)(0)
+    expect(None, MISSING, None, L.knz_encode_blocks, arr, 3)
+    expect(None, MISSING, None, L.knz_decode_blocks, arr, 3)
+    expect(None, MISSING, None, L.knz_dev_compress, src, len(data), len(data), dst, cap, o, None)
+    expect(None, MISSING, None, L.knz_dev_decompress, sp, len(good), back, len(data) + 64, o, None)
+    expect(None, MISSING, None, L.knz_dev_compress_blocks, src, len(data), dst, cap, o, None)
+    expect(None, MISSING, None, L.knz_dev_decompress_blocks, dst, 64, back, len(data) + 64, o, None)
+    expect(None, MISSING, None, L.knz_dev_assemble, len(data), segs1, bits1, 1, dst, cap, o, None)
+    expect(None, MISSING, None, L.knz_dev_compress_many, st1, 1, None)
+    expect(None, MISSING, None, L.knz_dev_decompress_many, st1, 1, None)
+    expect(None, MISSING, None, L.knz_transform_forward, 0, hp, 500, op, 4096, C.byref(n32))
+    expect(None, MISSING, None, L.knz_transform_inverse, 0, hp, 500, op, 4096, C.byref(n32))
+    expect(None, MISSING, None, L.knz_entropy_encode, et, hp, 500, op, 4096, o)
+    expect(None, MISSING, None, L.knz_entropy_decode, et, hp, 500, op, 500, o)
+    assert L.knz_close(None) == 0 and L.knz_lane_count(None) == 0
+    assert L.knz_last_timing(None, (C.c_float * 4)(), 4) == 0 and L.knz_last_counter(None, 0, o) == PARAM
+    assert L.knz_last_kernel_times(None, C.create_string_buffer(64), 64, (C.c_float * 4)(), 4) == 0
+    assert L.knz_last_lane_times(None, None, None, None, 0) == 0
+
+    for c in (one, two):
+        h = c.h
+        # ---- null d_dst, out_bytes, out_bits on the four knz_dev_* calls ----
+        expect(h, MISSING, None, L.knz_dev_compress, src, len(data), len(data), None, cap, o, None)
+        expect(h, MISSING, None, L.knz_dev_compress, src, len(data), len(data), dst, cap, None, None)
+        expect(h, MISSING, None, L.knz_dev_decompress, sp, len(good), None, len(data) + 64, o, None)
+        expect(h, MISSING, None, L.knz_dev_decompress, sp, len(good), back, len(data) + 64, None, None)
+        expect(h, MISSING, None, L.knz_dev_compress_blocks, src, len(data), None, cap, o, None)
+        expect(h, MISSING, None, L.knz_dev_compress_blocks, src, len(data), dst, cap, None, None)
+        expect(h, MISSING, None, L.knz_dev_decompress_blocks, dst, 64, None, len(data) + 64, o, None)
+        expect(h, MISSING, None, L.knz_dev_decompress_blocks, dst, 64, back, len(data) + 64, None, None)
+        # ---- a null `blocks` with n > 0, and n <= 0, on the two block calls ----
+        for fn in (L.knz_encode_blocks, L.knz_decode_blocks):
+            expect(h, MISSING, None, fn, None, 3)
+            expect(h, MISSING, None, fn, None, -1)
+            expect(h, 0, None, fn, None, 0)
+            expect(h, 0, None, fn, arr, 0)
+            expect(h, 0, None, fn, arr, -1)
+
+    # ---- alignment (on a lane of the two-lane handle the text stays on the lane) ----
+    for c in (one, two):
+        h, lane = c.h, c is two
+        t = "d_src must be 16-byte and d_dst 4-byte aligned"
+        expect(h, PARAM, None if lane else t, L.knz_dev_compress, src + 1, len(data) - 1, len(data) - 1, dst, cap, o, None)
+        expect(h, PARAM, None if lane else t, L.knz_dev_compress, src, len(data), len(data), dst + 1, cap - 1, o, None)
+        expect(h, PARAM, None if lane else t, L.knz_dev_compress_blocks, src + 1, len(data) - 1, dst, cap, o, None)
+        expect(h, PARAM, None if lane else t, L.knz_dev_compress_blocks, src, len(data), dst + 1, cap - 1, o, None)
+        t = "d_src must be 4-byte aligned"
+        expect(h, PARAM, None if lane else t, L.knz_dev_decompress, sp + 1, len(good) - 1, back, len(data) + 64, o, None)
+        expect(h, PARAM, None if lane else t, L.knz_dev_decompress_blocks, sp + 1, 64, back, len(data) + 64, o, None)
+    h = one.h
+    seg, kseg = be.empty(cap)
+    nbits = one.dev_compress_blocks(src, len(data), seg, cap)
+    segs, bits = (C.c_void_p * 1)(seg), (C.c_uint64 * 1)(nbits)
+    expect(h, PARAM, "d_dst must be 4-byte aligned", L.knz_dev_assemble, len(data), segs, bits, 1, dst + 1, cap - 1, o, None)
+    segs[0] = seg + 1
+    expect(h, PARAM, "segments must be 4-byte aligned", L.knz_dev_assemble, len(data), segs, bits, 1, dst, cap, o, None)
+    be.sync()
+    segs[0] = seg
+    expect(h, 0, None, L.knz_dev_assemble, len(data), segs, bits, 1, dst, cap, o, None)
+    assert be.to_host(kdst, out.value) == good
+
+    # ---- block descriptors ----
+    for c in (one, two):
+        h = c.h
+        arr, keep = block_array(parts, [4096] * 3)
+        arr[1].src = None
+        expect(h, PARAM, "invalid block descriptor", L.knz_encode_blocks, arr, 3)
+        arr, keep = block_array(parts, [4096] * 3)
+        arr[2].src_len = 0
+        expect(h, PARAM, "invalid block descriptor", L.knz_encode_blocks, arr, 3)
+        arr, keep = block_array([data[:bs + 16]], [4096])
+        expect(h, PARAM, "invalid block descriptor", L.knz_encode_blocks, arr, 1)
+        arr, keep = block_array([parts[2], parts[0], parts[1]], [4096] * 3)                # (two lanes: the short block leads the first lane's range of two)
+        expect(h, PARAM, "only the last block of a batch may be short", L.knz_encode_blocks, arr, 3)
+        arr, keep = block_array(parts, [4096] * 3)
+        arr[0].src_len = 0
+        expect(h, PARAM, "invalid block descriptor", L.knz_decode_blocks, arr, 3)
+
+    # ---- decoder inputs ----
+    h = one.h
+    expect(h, FILE, "stream too short", L.knz_dev_decompress, sp, 10, back, len(data) + 64, o, None)
+    bad, kbad = be.to_dev(bytes([good[0] ^ 0x40]) + good[1:], 4)
+    expect(h, FILE, "Invalid stream type", L.knz_dev_decompress, bad, len(good), back, len(data) + 64, o, None)
+    assert good[4] >> 4 == 6
+    bad, kbad = be.to_dev(good[:4] + bytes([0x50 | (good[4] & 15)]) + good[5:], 4)
+    expect(h, VERSION, "only bitstream version 6 is decoded on the device", L.knz_dev_decompress, bad, len(good), back, len(data) + 64, o, None)
+    out.value = 77
+    expect(h, 0, None, L.knz_dev_decompress_blocks, sp, 0, back, len(data) + 64, o, None)
+    assert out.value == 0
+
+    # ---- destinations too small ----
+    enc = [O.encode_block(p, tt, et) for p in parts]
+    for c in (one, two):
+        h = c.h
+        arr, keep = block_array(parts, [4096, 4, 4096])
+        expect(h, WRITE, "destination buffer too small", L.knz_encode_blocks, arr, 3)
+        assert [arr[i].status for i in range(3)] == [0, WRITE, 0]
+        for i in (0, 2):
+            assert arr[i].out_bits == enc[i]["written"] and keep[i][1][: len(enc[i]["bits"])].tobytes() == enc[i]["bits"]
+        arr, keep = block_array([e["bits"] for e in enc], [4096, 4, 4096])
+        expect(h, WRITE, "destination buffer too small", L.knz_decode_blocks, arr, 3)
+        assert [arr[i].status for i in range(3)] == [0, WRITE, 0]
+        for i in (0, 2):
+            assert arr[i].out_bits == len(parts[i]) and keep[i][1][: len(parts[i])].tobytes() == parts[i]
+    h = one.h
+    expect(h, WRITE, "destination buffer too small", L.knz_dev_compress, src, len(data), len(data), dst, 8, o, None)
+    expect(h, WRITE, "destination buffer too small", L.knz_entropy_encode, et, hp, 500, op, 1, o)
+
+    # ---- single objects ----
+    out.value = 77
+    expect(h, 0, None, L.knz_entropy_encode, et, hp, 0, op, 4096, o)
+    assert out.value == 0
+    out.value = 77
+    expect(h, 0, None, L.knz_entropy_decode, et, hp, 500, op, 0, o)
+    assert out.value == 0
+    t = "entropy codec has no device implementation in this build"
+    assert not L.knz_supports(0, 3)
+    expect(h, CODEC, t, L.knz_entropy_encode, 3, hp, 500, op, 4096, o)
+    expect(h, CODEC, t, L.knz_entropy_decode, 3, hp, 500, op, 500, o)
+    n32.value = 77
+    expect(h, 0, None, L.knz_transform_forward, 0, hp, 0, op, 4096, C.byref(n32))
+    assert n32.value == 0
+    expect(h, SKIP, None, L.knz_transform_forward, 0, hp, 500, op, 499, C.byref(n32))
+    expect(h, PROCESS, "Destination buffer too small", L.knz_transform_inverse, 0, hp, 500, op, 499, C.byref(n32))
+    t = "transform has no device implementation in this build"
+    expect(h, CODEC, t, L.knz_transform_forward, 63, hp, 500, op, 4096, C.byref(n32))
+    expect(h, CODEC, t, L.knz_transform_inverse, 63, hp, 500, op, 4096, C.byref(n32))
+    # the handles still work
+    assert one.dev_compress(src, len(data), dst, cap) == len(good) and be.to_host(kdst, len(good)) == good
+    assert K.BlockBatch(two).decode([e["bits"] for e in enc]) == parts
+    one.close()
+    two.close()

@@ -130,6 +130,10 @@ def test_codec_table(be):
     P.check_codec_table(be)
 
 
+def test_entry_point_contract(be):
+    P.check_entry_contract(be)
+
+
 def test_bwt_inverse_list_ranking(be, monkeypatch):
     P.check_bwt_list_ranking(be, monkeypatch, max_len=2100)
     monkeypatch.setenv("KNZ_BWT_RANK_MIN", "256")
