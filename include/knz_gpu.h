@@ -153,6 +153,55 @@ int knz_dev_compress_many(void* handle, knz_stream* streams, int n, void* hip_st
 int knz_dev_decompress_many(void* handle, knz_stream* streams, int n, void* hip_stream);
 
 /*
+ * Random access: the index of a stream, and the decode of a range of its blocks. What the Reader does with ctx["from"] / ctx["to"] (the CLI's
+ * --from / --to, v2/io/CompressedStream.go:1149-1160, :1859-1871: blocks outside the range have their frames read and dropped), device resident.
+ * Cost and workspace follow the range, not the stream: only the blocks of the range enter the decode batch.
+ *   knz_dev_stream_index:  parses the header (its errors) and walks the framing on the device (its errors: those of the whole-stream decode). Fills
+ *               info and pos[0 .. min(info->n_blocks, pos_cap)), a host array that may be NULL. info->n_blocks is always the true count: a second call
+ *               can size the array. A stream of header + end marker gives n_blocks 0 and returns 0. d_src as for knz_dev_decompress.
+ *   knz_dev_decompress_range: d_dst[0 .. *out_bytes) takes the decoded bytes of blocks from_block .. min(to_block, n_blocks + 1) - 1, from offset 0,
+ *               short inner blocks packed: byte for byte what knz_dev_decompress writes for those blocks. {1, KNZ_BLOCK_END, 0} is knz_dev_decompress
+ *               (bytes, out_bytes, error code). from_block == 0 or to_block <= from_block: KNZ_ERR_INVALID_PARAM. from_block behind the last block:
+ *               *out_bytes = 0, return 0 (the Reader skips every block and reports nothing). dst_cap holds the range as knz_dev_decompress's holds
+ *               the stream (block b of the range is decoded at b * block_size before short inner blocks are packed: for a stream a kanzi Writer
+ *               wrote that is the decoded bytes of the range and no more); too small: KNZ_ERR_WRITE_FILE, nothing is written behind dst_cap.
+ *               THE WALK ENDS ONCE THE LAST BLOCK OF THE RANGE IS LOCATED: framing behind the range is not read (the Reader reads every frame up
+ *               to the end marker; this one departure is what makes the call random access). Only the blocks of the range are decoded and checksum
+ *               verified: damage outside the range does not fail the call, damaged framing in front of it does, with the whole decode's code.
+ *               from_bit != 0: the walk starts at that bit as block from_block (the header is still parsed for the codec parameters). It is a hint
+ *               of an untrusted caller: >= 8 * n_bytes or in front of the first block gives KNZ_ERR_INVALID_PARAM; a wrong value inside the stream
+ *               behaves like damaged framing or a damaged block (an error code, or bytes that fail their checksum); the frame it names has to be a
+ *               block: an end marker there is damaged framing (KNZ_ERR_PROCESS_BLOCK), not an empty range. Whatever it says, every read
+ *               stays inside d_src[0 .. n_bytes) rounded up to 4 and every write inside dst_cap.
+ *   knz_dev_decompress_many_range: entry k behaves like knz_dev_decompress_range(streams[k], ranges[k]); everything else follows
+ *               knz_dev_decompress_many (status / out_bytes per entry, the first header's codec parameters, the lane of streams[0].d_dst, halves
+ *               on a refused workspace). The same d_src may appear in several entries. Only the words that hold an entry's selected blocks are
+ *               staged: a short range of a very long stream does not copy the stream.
+ *   KNZ_COUNTER_DECODE_BATCH_BLOCKS tells "decoded the range" from "decoded everything and sliced".
+ */
+typedef struct { uint64_t bit; uint64_t bits; } knz_block_pos;
+/* bit:  position in the stream of the block's FRAME: the 5-bit width field of Reader.processBlock (:1817). Block 1's equals header_bits.
+ * bits: payload bits behind the length field (`read`, :1818). */
+typedef struct {
+    uint64_t transform; uint32_t entropy, block_size, checksum_bits, bs_version;   /* as the header says */
+    int64_t  output_size;   /* the header's size field, 0 = the header has none */
+    uint32_t header_bits;   /* first bit behind the header */
+    uint32_t n_blocks;      /* frames in front of the end marker */
+    uint64_t end_bit;       /* first bit behind the end marker */
+} knz_stream_info;
+#define KNZ_BLOCK_END 0xFFFFFFFFu
+typedef struct {
+    uint32_t from_block, to_block;  /* block ids as the reference counts them: the first block is 1. from inclusive, to exclusive.
+                                       KNZ_BLOCK_END = through the last block */
+    uint64_t from_bit;              /* 0: walk from the header. Otherwise knz_block_pos.bit of block from_block, from an earlier index */
+} knz_block_range;
+int knz_dev_stream_index(void* handle, const void* d_src, uint64_t n_bytes, knz_stream_info* info,
+                         knz_block_pos* pos /* host, may be NULL */, uint32_t pos_cap, void* hip_stream);
+int knz_dev_decompress_range(void* handle, const void* d_src, uint64_t n_bytes, const knz_block_range* range,
+                             void* d_dst, uint64_t dst_cap, uint64_t* out_bytes, void* hip_stream);
+int knz_dev_decompress_many_range(void* handle, knz_stream* streams, const knz_block_range* ranges, int n, void* hip_stream);
+
+/*
  * Multi-GPU block sharding: a rank encodes blocks [first_block, first_block+n_blocks) of a
  * stream whose blocks are block_size bytes each; d_src points at this rank's first block. The result is a
  * bit string (no stream header, no end marker): *out_bits bits, zero padded to a byte in d_dst.
@@ -203,6 +252,8 @@ enum { KNZ_COUNTER_HUF_SERIAL_CHUNKS = 0, KNZ_COUNTER_POST_TRANSFORM_BYTES = 1 /
                                                decision the parallel layout leaves to the one-wave kernel): parsed by the one-wave kernel */,
        KNZ_COUNTER_LZ_FWD_ROUNDS = 5 /* rounds the fixed point of the last segment-parallel LZ forward stage took */,
        KNZ_COUNTER_RANK_PIPE_BLOCKS = 6 /* blocks of the last decode batch whose ZRLT / RANK inverses ran as one chain under the order-1 rANS decoder */,
+       KNZ_COUNTER_DECODE_BATCH_BLOCKS = 7 /* blocks that entered the last decode batch: a stream's block count after knz_dev_decompress, the blocks of
+                                              the range after a range call ; after a many call the sum over its entries, however many batches it took */,
        KNZ_COUNTER_STAGE_BYTES0 = 8 /* 8 + i: bytes that entered transform stage i (0..7) of the last encode batch, summed over its blocks */ };
 int knz_last_counter(void* handle, int id, uint64_t* value);
 

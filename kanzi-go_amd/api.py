@@ -57,6 +57,22 @@ class _Stream(C.Structure):
                 ("header_input_size", C.c_int64), ("out_bytes", C.c_uint64), ("status", C.c_int32), ("reserved", C.c_int32)]
 
 
+class _BlockPos(C.Structure):
+    _fields_ = [("bit", C.c_uint64), ("bits", C.c_uint64)]
+
+
+class _StreamInfo(C.Structure):
+    _fields_ = [("transform", C.c_uint64), ("entropy", C.c_uint32), ("block_size", C.c_uint32), ("checksum_bits", C.c_uint32),
+                ("bs_version", C.c_uint32), ("output_size", C.c_int64), ("header_bits", C.c_uint32), ("n_blocks", C.c_uint32), ("end_bit", C.c_uint64)]
+
+
+class _BlockRange(C.Structure):
+    _fields_ = [("from_block", C.c_uint32), ("to_block", C.c_uint32), ("from_bit", C.c_uint64)]
+
+
+BLOCK_END = 0xFFFFFFFF       # KNZ_BLOCK_END: a range through the last block
+
+
 def library_path():
     return os.environ.get("KNZ_GPU_LIB", os.path.join(_HERE, "libknz_gpu.so"))
 
@@ -103,6 +119,9 @@ def load_library(path=None):
     L.knz_dev_decompress.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, vp]
     L.knz_dev_compress_many.argtypes = [vp, C.POINTER(_Stream), C.c_int, vp]
     L.knz_dev_decompress_many.argtypes = [vp, C.POINTER(_Stream), C.c_int, vp]
+    L.knz_dev_stream_index.argtypes = [vp, vp, C.c_uint64, C.POINTER(_StreamInfo), C.POINTER(_BlockPos), C.c_uint32, vp]
+    L.knz_dev_decompress_range.argtypes = [vp, vp, C.c_uint64, C.POINTER(_BlockRange), vp, C.c_uint64, u64p, vp]
+    L.knz_dev_decompress_many_range.argtypes = [vp, C.POINTER(_Stream), C.POINTER(_BlockRange), C.c_int, vp]
     L.knz_dev_compress_blocks.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, vp]
     L.knz_dev_decompress_blocks.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, vp]
     L.knz_dev_assemble.argtypes = [vp, C.c_int64, C.POINTER(vp), u64p, C.c_int, vp, C.c_uint64, u64p, vp]
@@ -179,13 +198,39 @@ class Codec:
         self._chk(self.L.knz_dev_decompress(self.h, d_src, n_bytes, d_dst, dst_cap, C.byref(out), stream))
         return out.value
 
-    def _many(self, fn, items, check, stream):
+    def dev_stream_index(self, d_src, n_bytes, stream=0, pos_cap=None):
+        """The index of the .knz stream at d_src (knz_dev_stream_index) -> (info dict, [(bit, bits), ...]): the header's fields, header_bits, n_blocks and
+        end_bit, and per block the bit of its frame and its payload bits. pos_cap: rows to bring back (default: all, a second call sizes the array;
+        0 passes a NULL array); info["n_blocks"] is the true count either way."""
+        info = _StreamInfo()
+        if pos_cap is None:
+            self._chk(self.L.knz_dev_stream_index(self.h, d_src, n_bytes, C.byref(info), None, 0, stream))
+            pos_cap = info.n_blocks
+        pos = (_BlockPos * max(pos_cap, 1))()
+        self._chk(self.L.knz_dev_stream_index(self.h, d_src, n_bytes, C.byref(info), pos if pos_cap else None, pos_cap, stream))
+        d = {name: int(getattr(info, name)) for name, _t in _StreamInfo._fields_}
+        return d, [(int(pos[i].bit), int(pos[i].bits)) for i in range(min(pos_cap, info.n_blocks))]
+
+    def dev_decompress_range(self, d_src, n_bytes, d_dst, dst_cap, from_block, to_block=None, from_bit=0, stream=0):
+        """Blocks from_block .. to_block - 1 of the stream (the first block is 1; to_block None: through the last) decoded to d_dst from offset 0
+        (knz_dev_decompress_range). from_bit: 0, or the bit of block from_block's frame from dev_stream_index. Returns the bytes written."""
+        out = C.c_uint64()
+        rg = _BlockRange(from_block, BLOCK_END if to_block is None else to_block, from_bit)
+        self._chk(self.L.knz_dev_decompress_range(self.h, d_src, n_bytes, C.byref(rg), d_dst, dst_cap, C.byref(out), stream))
+        return out.value
+
+    def _many(self, fn, items, check, stream, ranged=False):
         n = len(items)
         arr = (_Stream * max(n, 1))()
+        rgs = (_BlockRange * max(n, 1))()
         for i, it in enumerate(items):
             arr[i].d_src, arr[i].n, arr[i].d_dst, arr[i].dst_cap = it[0], it[1], it[2], it[3]
+            if ranged:
+                rgs[i].from_block, rgs[i].to_block = it[4], BLOCK_END if (len(it) < 6 or it[5] is None) else it[5]
+                rgs[i].from_bit = it[6] if len(it) > 6 else 0
+                continue
             arr[i].header_input_size = it[4] if len(it) > 4 and it[4] is not None else (it[1] if fn is self.L.knz_dev_compress_many else 0)
-        rc = fn(self.h, arr, n, stream)
+        rc = fn(self.h, arr, rgs, n, stream) if ranged else fn(self.h, arr, n, stream)
         self.last_many_rc = rc
         if check:
             self._chk(rc)
@@ -200,6 +245,11 @@ class Codec:
     def dev_decompress_many(self, items, check=False, stream=0):
         """items: [(d_src, n_bytes, d_dst, dst_cap)], one .knz stream each (knz_dev_decompress_many). Returns [(out_bytes, status)]."""
         return self._many(self.L.knz_dev_decompress_many, items, check, stream)
+
+    def dev_decompress_many_range(self, items, check=False, stream=0):
+        """items: [(d_src, n_bytes, d_dst, dst_cap, from_block[, to_block[, from_bit]])], entry k as dev_decompress_range of it alone, all their blocks in one
+        device batch (knz_dev_decompress_many_range); the same d_src may appear in several entries. Returns [(out_bytes, status)]."""
+        return self._many(self.L.knz_dev_decompress_many_range, items, check, stream, ranged=True)
 
     def dev_compress_blocks(self, d_src, n, d_dst, dst_cap, stream=0):
         out = C.c_uint64()

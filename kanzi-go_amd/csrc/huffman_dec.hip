@@ -146,6 +146,55 @@ __global__ void knz_dec_walk_stream_kernel(WalkStreamArgs a) {
     a.result[1] = err;
 }
 
+// The same walk for a range of blocks (knz_dev_decompress_range) and for the index of a stream (knz_dev_stream_index): it starts at first_bit as block
+// first_id (ids as the reference counts them: the first block is 1), counts and skips the frames in front of `from`, records those of [from, to) and stops
+// behind the last of them, so framing behind the range is never read. Still one dependent chain (the lengths are in-line), bounded by nbytes exactly as
+// the walk above: every turn checks its frame against the stream's last bit before it moves on, whatever first_bit says.
+struct WalkRangeArgs {
+    const uint8_t* stream; uint64_t nbytes;
+    uint64_t first_bit;          // the frame of block first_id
+    uint64_t first_id, from, to; // to exclusive ; ~0: through the last block
+    uint32_t max_blocks;         // frames the walk may meet (knz_dec_walk_stream_kernel's bound and its error)
+    uint32_t cap;                // rows of blk_bit / blk_bits: blocks of the range beyond them are counted, not recorded
+    uint32_t frames;             // 1 (the index): blk_bit takes the frame's own first bit, its width field, instead of the payload's
+    uint32_t stride;             // row r at blk_bit[r * stride], blk_bits[r * stride] (the index interleaves them: knz_block_pos)
+    uint32_t hinted;             // 1: first_bit is a caller's hint: the frame it names has to be a block (an end marker there is damaged framing, not an empty range)
+    uint64_t* blk_bit; uint64_t* blk_bits;
+    uint64_t* result;            // [3] {blocks of the range, error code, bit behind the end marker (where the walk met it)}
+};
+
+__global__ void knz_dec_walk_range_kernel(WalkRangeArgs a) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    KnzStreamReader r;
+    r.init(a.stream, a.nbytes, a.first_bit);
+    const uint64_t limit = a.nbytes << 3;
+    uint64_t id = a.first_id, n = 0, end = 0;
+    uint32_t seen = 0, err = 0;
+    while (id < a.to) {
+        const uint64_t at = r.tell();
+        if (at + 8 > limit) { err = KNZ_ERR_PROCESS_BLOCK; break; }
+        const uint32_t lr = r.read(5) + 3;
+        uint64_t read = 0;
+        if (lr > 32) { read = (uint64_t)r.read(lr - 32) << 32; read |= r.read(32); }
+        else read = r.read(lr);
+        const uint64_t pos = r.tell();
+        if (read == 0) { end = pos; if (a.hinted && seen == 0) err = KNZ_ERR_PROCESS_BLOCK; break; }
+        if (read > ((uint64_t)1 << 34)) { err = KNZ_ERR_BLOCK_SIZE; break; }
+        if (pos + read > limit) { err = KNZ_ERR_PROCESS_BLOCK; break; }
+        if (seen >= a.max_blocks) { err = KNZ_ERR_BLOCK_SIZE; break; }
+        seen++;
+        if (id >= a.from) {
+            if (n < a.cap) { a.blk_bit[n * a.stride] = a.frames ? at : pos; a.blk_bits[n * a.stride] = read; }
+            n++;
+        }
+        id++;
+        r.seek(pos + read);
+    }
+    a.result[0] = n;
+    a.result[1] = err;
+    a.result[2] = end;
+}
+
 struct WalkBlocksArgs {
     const uint8_t* stream; uint64_t nbytes;
     const uint64_t* blk_bit; const uint64_t* blk_bits;

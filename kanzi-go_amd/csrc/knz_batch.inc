@@ -53,6 +53,13 @@ struct DecodeBatch {
           payload_only(0), given_len(0), entropy(c.entropy), checksum_bits(c.checksum_bits), block_size(c.block_size), transform(c.transform), total_out(0) {}
     // ... staged payloads instead of a stream: n of them, their bit positions already on the device (dec_stage_payloads, many.hip), block b decoded to out + b * stride
     void unframed(uint32_t n, uint64_t stride) { framed = 0; nblocks = n; out_stride = stride; }
+    // ... a range of the stream's blocks instead of all of them: the walk starts at `bit` as block first_id (the first block of a stream is 1), skips the
+    // frames in front of `from`, stops behind block to - 1 (~0: the last). Everything behind the walk is sized by the blocks it found: those of the range.
+    // hinted: `bit` is a caller's word, not the header's: the frame there has to be a block
+    bool ranged = false, rg_hinted = false; uint64_t rg_first_id = 1, rg_from = 1, rg_to = ~(uint64_t)0;
+    void range(uint64_t bit, uint64_t first_id, uint64_t from, uint64_t to, bool hinted) {
+        ranged = true; rg_hinted = hinted; first_bit = bit; rg_first_id = first_id; rg_from = from; rg_to = to;
+    }
     // block b failed with rc: true = stop at this first one ; with `many` it is marked, `first` keeps the first code and the batch goes on
     bool block_failed(uint32_t b, int rc, int& first) { status[b] = rc; if (!first) first = rc; return !many; }
 };
@@ -599,12 +606,25 @@ static int dec_walk_framing(Handle* h, DecodeBatch& db, hipStream_t st) {
         uint64_t bound = db.nbytes / 3 + 1;
         maxBlocks = (uint32_t)std::min<uint64_t>(bound, 1u << 24);
     }
+    const uint32_t walkBound = maxBlocks;
+    if (db.framed && db.ranged) maxBlocks = (uint32_t)std::min<uint64_t>(maxBlocks, db.rg_to - db.rg_from);   // (the tables hold the range, not the stream)
     DevBuf& blkBit = h->blk_dst_bit;      // reuse of the encode-side tables: [maxBlocks] u64 each
     DevBuf& blkBits = h->blk_written;
     if (blkBit.reserve(8 * ((size_t)maxBlocks + 1)) || blkBits.reserve(8 * ((size_t)maxBlocks + 1)) || h->total_bits.reserve(64))
         return knz_set_error(h, KNZ_ERR_CREATE_DECOMPRESSOR, "device workspace allocation failed");
     uint32_t nblocks = db.nblocks;
-    if (db.framed) {
+    if (db.framed && db.ranged) {
+        WalkRangeArgs wr;
+        wr.stream = db.d_stream; wr.nbytes = db.nbytes; wr.first_bit = db.first_bit; wr.first_id = db.rg_first_id; wr.from = db.rg_from; wr.to = db.rg_to;
+        wr.max_blocks = walkBound; wr.cap = maxBlocks; wr.frames = 0; wr.stride = 1; wr.hinted = db.rg_hinted ? 1 : 0;
+        wr.blk_bit = blkBit.as<uint64_t>(); wr.blk_bits = blkBits.as<uint64_t>(); wr.result = h->total_bits.as<uint64_t>();
+        hipLaunchKernelGGL(knz_dec_walk_range_kernel, dim3(1), dim3(1), 0, st, wr);
+        uint64_t* res = (uint64_t*)h->pinned;
+        HIP_OK(hipMemcpyAsync(res, h->total_bits.p, 24, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        if (res[1]) return knz_set_error(h, (int)res[1], "invalid block framing in stream");
+        nblocks = (uint32_t)res[0];
+    } else if (db.framed) {
         WalkStreamArgs ws;
         ws.stream = db.d_stream; ws.nbytes = db.nbytes; ws.first_bit = db.first_bit; ws.seg_bits = db.seg_bits; ws.max_blocks = maxBlocks;
         ws.blk_bit = blkBit.as<uint64_t>(); ws.blk_bits = blkBits.as<uint64_t>(); ws.result = h->total_bits.as<uint32_t>();
@@ -784,8 +804,10 @@ static int decode_batch(Handle* h, DecodeBatch& db, hipStream_t st) {
     if (!knz_supports(db.transform, db.entropy))
         return knz_set_error(h, KNZ_ERR_INVALID_CODEC, "transform/entropy combination has no device implementation in this build");
     const EntropyCodec& ec = *entropy_codec(db.entropy);
+    h->dec_blocks = 0;
     int rc = dec_walk_framing(h, db, st);
     if (rc || db.nblocks == 0) return rc;
+    h->dec_blocks = db.nblocks;
     DecStage d(h, db);
     if ((rc = dec_header_pass(h, d, ec, st)) != KNZ_OK) return rc;
     h->pipe_n = 0;

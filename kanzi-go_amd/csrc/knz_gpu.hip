@@ -286,11 +286,12 @@ static int sum_flags(const DevBuf& buf, size_t n, uint8_t only, uint64_t* value)
 
 extern "C" int knz_last_counter(void* handle, int id, uint64_t* value) {
     Handle* h = (Handle*)handle;
-    if (!h || !value || id < KNZ_COUNTER_HUF_SERIAL_CHUNKS || id > KNZ_COUNTER_STAGE_BYTES0 + 7 || (id > KNZ_COUNTER_RANK_PIPE_BLOCKS && id < KNZ_COUNTER_STAGE_BYTES0)) return KNZ_ERR_INVALID_PARAM;
+    if (!h || !value || id < KNZ_COUNTER_HUF_SERIAL_CHUNKS || id > KNZ_COUNTER_STAGE_BYTES0 + 7) return KNZ_ERR_INVALID_PARAM;
     if (h->multi) return multi_last_counter(h, id, value);
     DeviceGuard dg(h);
     *value = 0;
     if (id == KNZ_COUNTER_POST_TRANSFORM_BYTES) { *value = h->post_bytes; return KNZ_OK; }
+    if (id == KNZ_COUNTER_DECODE_BATCH_BLOCKS) { *value = h->dec_blocks; return KNZ_OK; }
     if (id >= KNZ_COUNTER_STAGE_BYTES0) { *value = h->stage_bytes[id - KNZ_COUNTER_STAGE_BYTES0]; return KNZ_OK; }
     if (id == KNZ_COUNTER_TEXT_CHAIN_BLOCKS) {
         uint32_t v = 0;

@@ -38,23 +38,42 @@ static int parse_stream_header(Handle* h, const uint8_t* hdr, uint64_t avail, kn
     return KNZ_OK;
 }
 
-extern "C" int knz_dev_decompress(void* handle, const void* d_src, uint64_t n_bytes, void* d_dst, uint64_t dst_cap,
-                                  uint64_t* out_bytes, void* hip_stream) {
+// the head of a stream at d_src, brought over and parsed: its codec parameters, size field and first block's bit
+static int read_stream_header(Handle* h, const void* d_src, uint64_t n_bytes, hipStream_t st, knz_cfg& sc, int64_t& outputSize, uint32_t& hbits) {
+    uint8_t hdr[32] = {0};
+    HIP_OK(hipMemcpyAsync(hdr, d_src, std::min<uint64_t>(32, n_bytes), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    return parse_stream_header(h, hdr, n_bytes, sc, outputSize, hbits);
+}
+
+// what a range asks for that can be refused before the device is asked (hbits: the first block's bit, from the stream's header)
+static int check_block_range(Handle* h, const knz_block_range& r, uint64_t n_bytes, uint32_t hbits) {
+    if (r.from_block == 0 || r.to_block <= r.from_block) return knz_set_error(h, KNZ_ERR_INVALID_PARAM, "invalid block range");
+    if (r.from_bit != 0 && (r.from_bit >= 8 * n_bytes || r.from_bit < hbits)) return knz_set_error(h, KNZ_ERR_INVALID_PARAM, "from_bit lies outside the stream's blocks");
+    return KNZ_OK;
+}
+
+// knz_dev_decompress and knz_dev_decompress_range: the whole stream (range == nullptr) or the blocks of a range, packed from d_dst on
+static int dev_decompress_stream(void* handle, const void* d_src, uint64_t n_bytes, const knz_block_range* range, void* d_dst, uint64_t dst_cap,
+                                 uint64_t* out_bytes, void* hip_stream) {
     Handle* h = lane_of_pointer((Handle*)handle, d_dst);
     if (!h || !d_src || !d_dst || !out_bytes) return KNZ_ERR_MISSING_PARAM;
     DeviceGuard dg(h);
     if ((uintptr_t)d_src & 3) return knz_set_error(h, KNZ_ERR_INVALID_PARAM, "d_src must be 4-byte aligned");
     hipStream_t st = dev_call_stream(h, hip_stream);
-    uint8_t hdr[32] = {0};
-    HIP_OK(hipMemcpyAsync(hdr, d_src, std::min<uint64_t>(32, n_bytes), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
     knz_cfg sc = h->cfg;
     int64_t outputSize = 0;
     uint32_t hbits = 0;
-    int rc = parse_stream_header(h, hdr, n_bytes, sc, outputSize, hbits);
+    int rc = read_stream_header(h, d_src, n_bytes, st, sc, outputSize, hbits);
     if (rc) return rc;
     DecodeBatch db(sc, (const uint8_t*)d_src, n_bytes, (uint8_t*)d_dst, dst_cap);   // (what the stream's header says, whatever the handle was opened with)
     db.first_bit = hbits;
+    if (range) {
+        if ((rc = check_block_range(h, *range, n_bytes, hbits)) != KNZ_OK) return rc;
+        const uint64_t to = range->to_block == KNZ_BLOCK_END ? ~(uint64_t)0 : range->to_block;
+        if (range->from_bit) db.range(range->from_bit, range->from_block, range->from_block, to, true);
+        else db.range(hbits, 1, range->from_block, to, false);
+    }
     rc = decode_batch(h, db, st);
     if (rc) return rc;
     // A kanzi Writer fills every block but the last (:536-560), and the batch placed block b at b * block_size. The Reader accepts
@@ -75,6 +94,52 @@ extern "C" int knz_dev_decompress(void* handle, const void* d_src, uint64_t n_by
         HIP_OK(hipStreamSynchronize(st));
     }
     *out_bytes = db.total_out;
+    return KNZ_OK;
+}
+
+extern "C" int knz_dev_decompress(void* handle, const void* d_src, uint64_t n_bytes, void* d_dst, uint64_t dst_cap,
+                                  uint64_t* out_bytes, void* hip_stream) {
+    return dev_decompress_stream(handle, d_src, n_bytes, nullptr, d_dst, dst_cap, out_bytes, hip_stream);
+}
+
+extern "C" int knz_dev_decompress_range(void* handle, const void* d_src, uint64_t n_bytes, const knz_block_range* range, void* d_dst, uint64_t dst_cap,
+                                        uint64_t* out_bytes, void* hip_stream) {
+    if (!range) return KNZ_ERR_MISSING_PARAM;
+    return dev_decompress_stream(handle, d_src, n_bytes, range, d_dst, dst_cap, out_bytes, hip_stream);
+}
+
+// The index of a stream: its header's fields, and the walk of knz_dev_decompress_range over every frame, recording where each starts. The count, the end
+// bit and the first pos_cap rows come back in one pinned copy.
+extern "C" int knz_dev_stream_index(void* handle, const void* d_src, uint64_t n_bytes, knz_stream_info* info, knz_block_pos* pos, uint32_t pos_cap,
+                                    void* hip_stream) {
+    Handle* h = lane_of_pointer((Handle*)handle, d_src);
+    if (!h || !d_src || !info) return KNZ_ERR_MISSING_PARAM;
+    DeviceGuard dg(h);
+    if ((uintptr_t)d_src & 3) return knz_set_error(h, KNZ_ERR_INVALID_PARAM, "d_src must be 4-byte aligned");
+    hipStream_t st = dev_call_stream(h, hip_stream);
+    knz_cfg sc = h->cfg;
+    int64_t outputSize = 0;
+    uint32_t hbits = 0;
+    int rc = read_stream_header(h, d_src, n_bytes, st, sc, outputSize, hbits);
+    if (rc) return rc;
+    const uint32_t bound = (uint32_t)std::min<uint64_t>(n_bytes / 3 + 1, 1u << 24);       // (dec_walk_framing's: 8 framing + 16 payload bits a block at least)
+    const uint32_t cap = pos ? std::min(pos_cap, bound) : 0;
+    const size_t bytes = 8 * (4 + 2 * (size_t)cap);
+    if (h->blk_dst_bit.reserve(bytes)) return knz_set_error(h, KNZ_ERR_CREATE_DECOMPRESSOR, "device workspace allocation failed");
+    if (h->pinned_rows.reserve(bytes)) return knz_set_error(h, KNZ_ERR_CREATE_DECOMPRESSOR, "pinned host allocation failed");
+    WalkRangeArgs wr;
+    wr.stream = (const uint8_t*)d_src; wr.nbytes = n_bytes; wr.first_bit = hbits; wr.first_id = 1; wr.from = 1; wr.to = ~(uint64_t)0;
+    wr.max_blocks = bound; wr.cap = cap; wr.frames = 1; wr.stride = 2; wr.hinted = 0;
+    wr.result = h->blk_dst_bit.as<uint64_t>(); wr.blk_bit = wr.result + 4; wr.blk_bits = wr.result + 5;
+    hipLaunchKernelGGL(knz_dec_walk_range_kernel, dim3(1), dim3(1), 0, st, wr);
+    const uint64_t* res = h->pinned_rows.as<uint64_t>();
+    HIP_OK(hipMemcpyAsync(h->pinned_rows.p, h->blk_dst_bit.p, bytes, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    HIP_OK(hipGetLastError());
+    if (res[1]) return knz_set_error(h, (int)res[1], "invalid block framing in stream");
+    info->transform = sc.transform; info->entropy = sc.entropy; info->block_size = sc.block_size; info->checksum_bits = sc.checksum_bits; info->bs_version = 6;
+    info->output_size = outputSize; info->header_bits = hbits; info->n_blocks = (uint32_t)res[0]; info->end_bit = res[2];
+    if (pos) memcpy(pos, res + 4, sizeof(knz_block_pos) * (size_t)std::min<uint64_t>(res[0], cap));
     return KNZ_OK;
 }
 

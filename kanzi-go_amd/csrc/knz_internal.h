@@ -60,6 +60,7 @@ struct Handle {
     int nprobes = 0;
     uint64_t stage_bytes[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // bytes that entered transform stage i of the last encode batch (knz_last_counter 8 + i)
     DevBuf stage_sum;                 // their device-side sums
+    uint64_t dec_blocks = 0;          // blocks that entered the last decode batch (knz_last_counter 7)
     uint64_t post_bytes = 0;          // bytes behind the transform sequence of the last encode batch (entropy coder input)
     int device = 0;
     hipStream_t stream = nullptr;
@@ -101,7 +102,8 @@ struct Handle {
     DevBuf sa_keys0, sa_keys1, sa_vals0, sa_vals1, sa_rank, sa_gs, sa_head, sa_unres, sa_pos, sa_tmp, sa_links, sa_sp;
     DevBuf sa_hb, sa_tiles, sa_posl0, sa_posl1, sa_gid0, sa_gid1;   // suffix sort (bwt_sort.hip): head bits, per-tile tables, the large list
     DevBuf many_tab, many_blk_stream, many_blk_pos, many_heads;     // several streams in one batch (many.hip): table of streams, owner and place of every block, the streams' heads
-    PinnedBuf many_pinned;            // ... the table of streams (and the heads) on the host
+    DevBuf many_ranges;               // ... and the table of ranges of a range call
+    PinnedBuf many_pinned;            // ... the table of streams (and the heads, or the ranges) on the host
     void* pinned = nullptr;           // small pinned host area for results
     // results of the last encode batch, one row per block + the batch totals behind them: packed on the device (knz_pack_results_kernel), ONE copy into pinned memory
     struct ResultRow { uint64_t written; uint64_t cksum; uint32_t post_len; int32_t status; uint32_t mode; uint32_t skip; };

@@ -86,7 +86,11 @@ extern "C" int knz_dev_compress_many(void* handle, knz_stream* streams, int n, v
     return many_end(h, streams, n);
 }
 
-static int decompress_many_once(Handle* h, knz_stream* s, const uint32_t* firstBit, const knz_cfg& sc, int n, hipStream_t st) {
+// rg == nullptr: every stream whole, staged side by side. Else entry k's range rg[k]: the walkers read the callers' buffers, and only the bytes that hold
+// the selected frames are staged (knz_many_stage_range_kernel), so that walk, staging and batch follow the ranges and not the streams.
+// entered: the blocks of these entries that went into a decode batch (the first pass: a later one runs fewer of the same).
+static int decompress_many_once(Handle* h, knz_stream* s, const uint32_t* firstBit, const knz_block_range* rg, const knz_cfg& sc, int n, hipStream_t st, uint64_t& entered) {
+    uint64_t first_pass = 0;
     std::vector<int> active;
     std::vector<int32_t> status(n, 0);
     std::vector<uint64_t> out(n, 0);
@@ -94,38 +98,73 @@ static int decompress_many_once(Handle* h, knz_stream* s, const uint32_t* firstB
     const uint64_t ostride = ((uint64_t)sc.block_size + 63) & ~(uint64_t)63;
     while (!active.empty()) {
         const int A = (int)active.size();
-        if (h->many_pinned.reserve(sizeof(ManyStream) * (size_t)A)) return knz_set_error(h, KNZ_ERR_CREATE_DECOMPRESSOR, "pinned host allocation failed");
+        const size_t tabBytes = sizeof(ManyStream) * (size_t)A, rgBytes = rg ? sizeof(ManyRange) * (size_t)A : 0;
+        if (h->many_pinned.reserve(tabBytes + rgBytes)) return knz_set_error(h, KNZ_ERR_CREATE_DECOMPRESSOR, "pinned host allocation failed");
         ManyStream* tab = h->many_pinned.as<ManyStream>();
+        ManyRange* rtab = (ManyRange*)(h->many_pinned.as<uint8_t>() + tabBytes);
         uint64_t staged = 0;
         for (int i = 0; i < A; i++) {
             const knz_stream& c = s[active[i]];
             ManyStream& m = tab[i];
             memset(&m, 0, sizeof(m));
             m.src = (uint64_t)c.d_src; m.n = c.n; m.dst = (uint64_t)c.d_dst; m.cap = c.dst_cap; m.hdr_bits = firstBit[active[i]]; m.stage_off = staged;
-            staged += (c.n + 15) & ~(uint64_t)15;
+            if (!rg) { staged += (c.n + 15) & ~(uint64_t)15; continue; }
+            const knz_block_range& r = rg[active[i]];                     // (a range's place in the staging buffer: once the count walk has found its frames)
+            ManyRange& g = rtab[i];
+            memset(&g, 0, sizeof(g));
+            g.from = r.from_block; g.to = r.to_block; g.start_bit = r.from_bit ? r.from_bit : m.hdr_bits; g.start_id = r.from_bit ? r.from_block : 1; g.hinted = r.from_bit ? 1 : 0;
         }
-        if (h->many_tab.reserve(sizeof(ManyStream) * (size_t)A) || h->stage_in.reserve(staged + 64) || h->total_bits.reserve(64))
+        if (h->many_tab.reserve(tabBytes) || (rg ? h->many_ranges.reserve(rgBytes) : h->stage_in.reserve(staged + 64)) || h->total_bits.reserve(64))
             return knz_set_error(h, KNZ_ERR_CREATE_DECOMPRESSOR, "device workspace allocation failed");
         ManyStream* dtab = h->many_tab.as<ManyStream>();
-        HIP_OK(hipMemcpyAsync(dtab, tab, sizeof(ManyStream) * (size_t)A, hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemsetAsync(h->stage_in.as<uint8_t>() + staged, 0, 64, st));
-        uint64_t longest = 0;
-        for (int i = 0; i < A; i++) longest = std::max(longest, tab[i].n);
-        hipLaunchKernelGGL(knz_many_stage_kernel, dim3(A, many_copy_y(longest)), dim3(256), 0, st, (const ManyStream*)dtab, h->stage_in.as<uint8_t>());
+        ManyRange* drg = h->many_ranges.as<ManyRange>();
+        HIP_OK(hipMemcpyAsync(dtab, tab, tabBytes, hipMemcpyHostToDevice, st));
         ManyWalkArgs w;
-        w.streams = dtab; w.K = (uint32_t)A; w.stage = h->stage_in.as<uint8_t>(); w.fill = 0; w.blk_bit = nullptr; w.blk_bits = nullptr; w.blk_stream = nullptr;
-        hipLaunchKernelGGL(knz_many_walk_kernel, dim3((A + 63) / 64), dim3(64), 0, st, w);
+        w.streams = dtab; w.K = (uint32_t)A; w.stage = nullptr; w.fill = 0; w.blk_bit = nullptr; w.blk_bits = nullptr; w.blk_stream = nullptr;
+        if (!rg) {
+            HIP_OK(hipMemsetAsync(h->stage_in.as<uint8_t>() + staged, 0, 64, st));
+            uint64_t longest = 0;
+            for (int i = 0; i < A; i++) longest = std::max(longest, tab[i].n);
+            hipLaunchKernelGGL(knz_many_stage_kernel, dim3(A, many_copy_y(longest)), dim3(256), 0, st, (const ManyStream*)dtab, h->stage_in.as<uint8_t>());
+            w.stage = h->stage_in.as<uint8_t>();
+            hipLaunchKernelGGL(knz_many_walk_kernel, dim3((A + 63) / 64), dim3(64), 0, st, w);
+        } else {
+            HIP_OK(hipMemcpyAsync(drg, rtab, rgBytes, hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(knz_many_walk_range_kernel, dim3((A + 63) / 64), dim3(64), 0, st, w, drg);
+        }
         hipLaunchKernelGGL(knz_many_scan_kernel, dim3(1), dim3(256), 0, st, dtab, (uint32_t)A, (uint64_t)sc.block_size, 0u, h->total_bits.as<uint32_t>() + 8);
-        HIP_OK(hipMemcpyAsync(tab, dtab, sizeof(ManyStream) * (size_t)A, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(tab, dtab, tabBytes, hipMemcpyDeviceToHost, st));
+        if (rg) HIP_OK(hipMemcpyAsync(rtab, drg, rgBytes, hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
         uint64_t nblocks = 0;
         for (int i = 0; i < A; i++) { status[active[i]] = tab[i].status; nblocks += tab[i].nblocks; }      // (a stream with damaged framing: its status, no blocks)
         if (nblocks == 0) break;
+        first_pass = std::max(first_pass, nblocks);
         if (h->blk_dst_bit.reserve(8 * (nblocks + 1)) || h->blk_written.reserve(8 * (nblocks + 1)) || h->many_blk_stream.reserve(4 * (nblocks + 1)) ||
             h->many_blk_pos.reserve(8 * (nblocks + 1)) || h->stage_out.reserve(ostride * nblocks + 64))
             return knz_set_error(h, KNZ_ERR_CREATE_DECOMPRESSOR, "device workspace allocation failed");
+        if (rg) {
+            // the bytes that hold every entry's selected frames, side by side: from the 16 bytes its first payload bit lies in to its last payload byte
+            uint64_t longest = 0;
+            for (int i = 0; i < A; i++) {
+                ManyStream& m = tab[i];
+                ManyRange& g = rtab[i];
+                if (m.status || !m.nblocks) continue;
+                if (g.span_lo > g.span_hi || g.span_hi > 8 * m.n) return knz_set_error(h, KNZ_ERR_UNKNOWN, "framing walk left the stream");   // (the walk checks every frame)
+                g.src_off = (g.span_lo >> 3) & ~(uint64_t)15; g.len = ((g.span_hi + 7) >> 3) - g.src_off;
+                m.stage_off = staged;
+                staged += (g.len + 15) & ~(uint64_t)15;
+                longest = std::max(longest, g.len);
+            }
+            if (h->stage_in.reserve(staged + 64)) return knz_set_error(h, KNZ_ERR_CREATE_DECOMPRESSOR, "device workspace allocation failed");
+            HIP_OK(hipMemcpyAsync(dtab, tab, tabBytes, hipMemcpyHostToDevice, st));
+            HIP_OK(hipMemcpyAsync(drg, rtab, rgBytes, hipMemcpyHostToDevice, st));
+            HIP_OK(hipMemsetAsync(h->stage_in.as<uint8_t>() + staged, 0, 64, st));
+            KNZ_LAUNCH_PROBED(knz_many_stage_range_kernel, dim3(A, many_copy_y(longest)), dim3(256), 0, st, (const ManyStream*)dtab, (const ManyRange*)drg, h->stage_in.as<uint8_t>());
+        }
         w.fill = 1; w.blk_bit = h->blk_dst_bit.as<uint64_t>(); w.blk_bits = h->blk_written.as<uint64_t>(); w.blk_stream = h->many_blk_stream.as<uint32_t>();
-        hipLaunchKernelGGL(knz_many_walk_kernel, dim3((A + 63) / 64), dim3(64), 0, st, w);
+        if (rg) hipLaunchKernelGGL(knz_many_walk_range_kernel, dim3((A + 63) / 64), dim3(64), 0, st, w, drg);
+        else hipLaunchKernelGGL(knz_many_walk_kernel, dim3((A + 63) / 64), dim3(64), 0, st, w);
         DecodeBatch db(sc, h->stage_in.as<uint8_t>(), staged, h->stage_out.as<uint8_t>(), ostride * nblocks);
         db.unframed((uint32_t)nblocks, ostride); db.many = true;
         const int rc = decode_batch(h, db, st);
@@ -156,14 +195,17 @@ static int decompress_many_once(Handle* h, knz_stream* s, const uint32_t* firstB
         break;
     }
     for (int k = 0; k < n; k++) if (s[k].status == 0) { s[k].status = status[k]; s[k].out_bytes = out[k]; }
+    entered += first_pass;
     return KNZ_OK;
 }
 
-extern "C" int knz_dev_decompress_many(void* handle, knz_stream* streams, int n, void* hip_stream) {
+// knz_dev_decompress_many (ranges == nullptr) and knz_dev_decompress_many_range
+static int dev_decompress_many(void* handle, knz_stream* streams, const knz_block_range* ranges, int n, void* hip_stream) {
     if (!handle || (!streams && n > 0)) return KNZ_ERR_MISSING_PARAM;
     if (n <= 0) return KNZ_OK;
     Handle* h = many_begin(handle, streams, n, false);
     DeviceGuard dg(h);
+    h->dec_blocks = 0;
     hipStream_t st = dev_call_stream(h, hip_stream);
     // every stream's head: one device-side gather, one copy into pinned memory; the headers are parsed here as knz_dev_decompress parses one
     const size_t tabBytes = sizeof(ManyStream) * (size_t)n;
@@ -194,7 +236,20 @@ extern "C" int knz_dev_decompress_many(void* handle, knz_stream* streams, int n,
         if (sc.transform != msc.transform || sc.entropy != msc.entropy || sc.block_size != msc.block_size || sc.checksum_bits != msc.checksum_bits)
             streams[k].status = KNZ_ERR_INVALID_PARAM;                    // one batch, one set of codec parameters: the first stream's
     }
+    for (int k = 0; k < n && ranges; k++)
+        if (streams[k].status == 0) streams[k].status = check_block_range(h, ranges[k], streams[k].n, firstBit[k]);
+    uint64_t entered = 0;                                                 // (knz_last_counter 7: over every batch of the call, halves and second passes included)
     if (have)
-        many_split_retry(h, streams, n, st, [&](int lo, int cnt) { return decompress_many_once(h, streams + lo, firstBit.data() + lo, msc, cnt, st); });
+        many_split_retry(h, streams, n, st, [&](int lo, int cnt) { return decompress_many_once(h, streams + lo, firstBit.data() + lo, ranges ? ranges + lo : nullptr, msc, cnt, st, entered); });
+    h->dec_blocks = entered;
     return many_end(h, streams, n);
+}
+
+extern "C" int knz_dev_decompress_many(void* handle, knz_stream* streams, int n, void* hip_stream) {
+    return dev_decompress_many(handle, streams, nullptr, n, hip_stream);
+}
+
+extern "C" int knz_dev_decompress_many_range(void* handle, knz_stream* streams, const knz_block_range* ranges, int n, void* hip_stream) {
+    if (!ranges && n > 0) return KNZ_ERR_MISSING_PARAM;
+    return dev_decompress_many(handle, streams, ranges, n, hip_stream);
 }

@@ -170,13 +170,9 @@ __global__ void knz_many_heads_kernel(const ManyStream* s, uint32_t K, uint32_t*
 
 // grid (K, y): stream k's n bytes to stage + stage_off, zero filled to the next multiple of 16. 16-byte accesses where the source allows
 // them, 4-byte words elsewhere (the destination is 16-byte aligned; the bytes behind n are cleared).
-__global__ __launch_bounds__(256) void knz_many_stage_kernel(const ManyStream* s, uint8_t* stage) {
-    const ManyStream& m = s[blockIdx.x];
-    if (m.status != 0) return;
-    const uint8_t* src = (const uint8_t*)m.src;
-    uint8_t* dst = stage + m.stage_off;
-    const uint64_t n = m.n, units = (n + 15) >> 4;
-    const bool aligned = (m.src & 15) == 0;
+__device__ __forceinline__ void knz_many_stage_bytes(const uint8_t* src, uint8_t* dst, const uint64_t n) {
+    const uint64_t units = (n + 15) >> 4;
+    const bool aligned = ((uint64_t)src & 15) == 0;
     for (uint64_t u = (uint64_t)blockIdx.y * 256 + threadIdx.x; u < units; u += (uint64_t)gridDim.y * 256) {
         const uint64_t o = u << 4;
         if (aligned && o + 16 <= n) { *(uint4*)(dst + o) = *(const uint4*)(src + o); continue; }
@@ -189,6 +185,30 @@ __global__ __launch_bounds__(256) void knz_many_stage_kernel(const ManyStream* s
             *(uint32_t*)(dst + q) = v;
         }
     }
+}
+__global__ __launch_bounds__(256) void knz_many_stage_kernel(const ManyStream* s, uint8_t* stage) {
+    const ManyStream& m = s[blockIdx.x];
+    if (m.status != 0) return;
+    knz_many_stage_bytes((const uint8_t*)m.src, stage + m.stage_off, m.n);
+}
+
+// One row per entry of knz_dev_decompress_many_range, next to its ManyStream row. The count walk finds where the selected frames lie, the host
+// turns that into the bytes to stage (src_off a multiple of 16, so that 16-byte copies stay possible where the caller's pointer allows them).
+struct ManyRange {
+    uint32_t from, to;               // block ids, the first block is 1 ; to exclusive, 0xFFFFFFFF: through the last block
+    uint64_t start_bit;              // the count walk starts at this frame, as block start_id (the header's end as 1, or the caller's hint as `from`)
+    uint32_t start_id, hinted;       // hinted: start_bit is the caller's, the frame it names has to be a block
+    uint64_t first_frame;            // count walk: the frame of block `from`, where the fill walk starts
+    uint64_t span_lo, span_hi;       // count walk: the bits of the stream that hold the selected payloads
+    uint64_t src_off, len;           // host: the bytes [src_off, src_off + len) of the stream go to stage + stage_off
+};
+
+// grid (K, y): ... for a range call: only the bytes that cover entry k's selected frames, however long the stream around them is
+__global__ __launch_bounds__(256) void knz_many_stage_range_kernel(const ManyStream* s, const ManyRange* rg, uint8_t* stage) {
+    const ManyStream& m = s[blockIdx.x];
+    if (m.status != 0 || m.nblocks == 0) return;
+    const ManyRange& g = rg[blockIdx.x];
+    knz_many_stage_bytes((const uint8_t*)m.src + g.src_off, stage + m.stage_off, g.len);
 }
 
 struct ManyWalkArgs {
@@ -225,6 +245,51 @@ __global__ void knz_many_walk_kernel(ManyWalkArgs a) {
         r.seek(pos + read);
     }
     if (!a.fill) { s.nblocks = err ? 0 : n; s.status = (int32_t)err; }
+}
+
+// ... with a range per stream (knz_dec_walk_range_kernel side by side). The walkers read the CALLER's buffers, each bounded by its own stream's n bytes:
+// nothing is staged before it is known which bytes hold the selected frames. count: frames in front of `from` are skipped, the walk stops behind the last
+// block of the range and leaves where its frames lie ; fill: from the first selected frame on, positions rebased to the entry's bytes in the staging buffer.
+__global__ void knz_many_walk_range_kernel(ManyWalkArgs a, ManyRange* rg) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= a.K) return;
+    ManyStream& s = a.streams[k];
+    if (s.status != 0) return;
+    ManyRange& g = rg[k];
+    const uint64_t limit = s.n << 3;
+    const uint64_t maxBlocks = min(s.n / 3 + 1, (uint64_t)1 << 24);
+    const uint64_t to = a.fill ? (uint64_t)g.from + s.nblocks : (g.to == 0xFFFFFFFFu ? ~(uint64_t)0 : (uint64_t)g.to);
+    const uint64_t rebase = (s.stage_off << 3) - (g.src_off << 3);       // (fill: modulo 2^64, src_off * 8 <= every position)
+    uint64_t id = a.fill ? g.from : g.start_id;
+    KnzStreamReader r;
+    r.init((const uint8_t*)s.src, s.n, a.fill ? g.first_frame : g.start_bit);
+    uint32_t n = 0, seen = 0, err = 0;
+    uint64_t first = 0, lo = 0, hi = 0;
+    while (id < to) {                                                    // every turn moves at least 8 bits ahead, or ends the walk
+        const uint64_t at = r.tell();
+        if (at + 8 > limit) { err = KNZ_ERR_PROCESS_BLOCK; break; }
+        const uint32_t lr = r.read(5) + 3;
+        uint64_t read = 0;
+        if (lr > 32) { read = (uint64_t)r.read(lr - 32) << 32; read |= r.read(32); }
+        else read = r.read(lr);
+        if (read == 0) { if (!a.fill && g.hinted && seen == 0) err = KNZ_ERR_PROCESS_BLOCK; break; }
+        if (read > ((uint64_t)1 << 34)) { err = KNZ_ERR_BLOCK_SIZE; break; }
+        const uint64_t pos = r.tell();
+        if (pos + read > limit) { err = KNZ_ERR_PROCESS_BLOCK; break; }
+        if (seen >= maxBlocks) { err = KNZ_ERR_BLOCK_SIZE; break; }
+        seen++;
+        if (id >= g.from) {
+            if (a.fill) { a.blk_bit[s.first_block + n] = pos + rebase; a.blk_bits[s.first_block + n] = read; a.blk_stream[s.first_block + n] = k; }
+            else { if (n == 0) { first = at; lo = pos; } hi = pos + read; }
+            n++;
+        }
+        id++;
+        r.seek(pos + read);
+    }
+    if (!a.fill) {
+        s.nblocks = err ? 0 : n; s.status = (int32_t)err;
+        g.first_frame = first; g.span_lo = lo; g.span_hi = hi;
+    }
 }
 
 struct ManyPlaceArgs {
