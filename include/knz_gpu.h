@@ -202,6 +202,56 @@ int knz_dev_decompress_range(void* handle, const void* d_src, uint64_t n_bytes, 
 int knz_dev_decompress_many_range(void* handle, knz_stream* streams, const knz_block_range* ranges, int n, void* hip_stream);
 
 /*
+ * Byte reads: K triples (source, byte offset, length) and K destinations, a ReadAt over .knz streams. The covering blocks are decoded once, in one
+ * batch, and the bytes land where they were asked for; no block ids, no block-sized destinations, no second copy.
+ *   addressing: byte `offset` lies in block offset / block_size + 1 at offset % block_size; block_size comes from the stream's header. For a stream a
+ *               kanzi Writer wrote, only the last block is short: the offset is then the offset in the decoded stream, and d_dst[0 .. out_bytes) equals
+ *               knz_dev_decompress(...)[offset .. offset + out_bytes). A read delivers bytes in order until its length is served or it meets the end
+ *               of a block that decoded to fewer than block_size bytes (the stream's last block, or a short inner block): it ends there with status 0
+ *               and out_bytes < length, like a short ReadAt. It never delivers a byte from a wrong position. Zero bytes with status 0 are the answer
+ *               for an offset at or behind the end, an offset behind a block's decoded length, and length == 0. Blocks in front of a read's first
+ *               block are neither decoded nor checked, framing behind its last block is not read (the departure of knz_dev_decompress_range).
+ *   once:       the batch holds every distinct (source, block) pair that some read touches, once, however many reads touch it;
+ *               KNZ_COUNTER_DECODE_BATCH_BLOCKS reports that number. Two knz_source rows with the same d_src are two sources.
+ *   results:    a read's result depends only on its own source and window (the blocks offset / block_size + 1 .. (offset + length - 1) / block_size + 1),
+ *               not on what else is in the call or in what order. A read whose window holds a failing block (damaged payload, checksum mismatch,
+ *               decoded length above the block size) takes that block's code, the one knz_dev_decompress_range gives for that block alone (the first
+ *               such block's, in block order): out_bytes = 0 and NOTHING of its destination is written. A read whose window lies in other blocks of
+ *               the same stream completes. Damaged framing in front of a read's first block fails that read with the walk's code (the walk starts at
+ *               the header, or at the hinted frame).
+ *   sources:    headers are parsed as knz_dev_decompress_many parses them: the first parsable header's transform, entropy codec, block size and
+ *               checksum size rule the call, a source that differs gets KNZ_ERR_INVALID_PARAM. A source's non-zero status (its header's code, a NULL
+ *               d_src: KNZ_ERR_MISSING_PARAM, a d_src off 4 bytes: KNZ_ERR_INVALID_PARAM) is the status of all its reads.
+ *   hints:      with pos present, the walk for block b <= n_pos starts at pos[b-1].bit (knz_block_range.from_bit, checked as there); blocks behind
+ *               n_pos walk from the header. Hints come from an untrusted caller: one outside the stream (>= 8 * n, or in front of the header's
+ *               end) gives KNZ_ERR_INVALID_PARAM on the reads that use it, a wrong one inside the stream an error code or that frame's bytes.
+ *               Whatever the hint says, every read stays inside d_src[0 .. n) rounded up to 4, and every write inside d_dst[0 .. length).
+ *   writes:     exactly the bytes d_dst[0 .. out_bytes) of each read are written. Destinations of different reads may be adjacent to the byte, as in
+ *               a packed output tensor, at any alignment. Overlapping destinations are the caller's mistake and undefined.
+ *   arguments:  offset + length overflowing, or source >= n_sources: KNZ_ERR_INVALID_PARAM on that read. NULL reads or sources (n_reads > 0): the
+ *               call returns KNZ_ERR_MISSING_PARAM; a NULL d_dst with length > 0: KNZ_ERR_MISSING_PARAM on that read. n_reads <= 0 returns 0.
+ *               The call returns 0 or the status of the first read (lowest index) that failed.
+ *   workspace:  a read list whose workspace the device refuses is taken in halves, by the many calls' rule (a block that both halves touch is then
+ *               decoded in each). On a handle of several lanes the call runs on the lane that owns reads[0].d_dst.
+ *   knz_dev_read: one source, one read, no hint.
+ */
+typedef struct {
+    const void* d_src; uint64_t n;             /* one .knz stream, device; alignment and readability as knz_dev_decompress's d_src */
+    const knz_block_pos* pos; uint32_t n_pos;  /* host, may be NULL / 0: rows 0 .. n_pos-1 of knz_dev_stream_index for this stream (blocks 1 .. n_pos) */
+    int32_t status;                            /* result: 0, or the code of this stream's header / pointer check; its reads take it */
+} knz_source;
+typedef struct {
+    uint32_t source, reserved;                 /* index into sources[] */
+    uint64_t offset, length;                   /* bytes of the decoded stream */
+    void*    d_dst;                            /* device, ANY alignment, `length` bytes writable */
+    uint64_t out_bytes;                        /* result */
+    int32_t  status, reserved2;                /* result: 0 or a kanzi error code */
+} knz_read;
+int knz_dev_read_many(void* handle, knz_source* sources, int n_sources, knz_read* reads, int n_reads, void* hip_stream);
+int knz_dev_read(void* handle, const void* d_src, uint64_t n_bytes, uint64_t offset, uint64_t length,
+                 void* d_dst, uint64_t* out_bytes, void* hip_stream);
+
+/*
  * Multi-GPU block sharding: a rank encodes blocks [first_block, first_block+n_blocks) of a
  * stream whose blocks are block_size bytes each; d_src points at this rank's first block. The result is a
  * bit string (no stream header, no end marker): *out_bits bits, zero padded to a byte in d_dst.
@@ -253,7 +303,8 @@ enum { KNZ_COUNTER_HUF_SERIAL_CHUNKS = 0, KNZ_COUNTER_POST_TRANSFORM_BYTES = 1 /
        KNZ_COUNTER_LZ_FWD_ROUNDS = 5 /* rounds the fixed point of the last segment-parallel LZ forward stage took */,
        KNZ_COUNTER_RANK_PIPE_BLOCKS = 6 /* blocks of the last decode batch whose ZRLT / RANK inverses ran as one chain under the order-1 rANS decoder */,
        KNZ_COUNTER_DECODE_BATCH_BLOCKS = 7 /* blocks that entered the last decode batch: a stream's block count after knz_dev_decompress, the blocks of
-                                              the range after a range call ; after a many call the sum over its entries, however many batches it took */,
+                                              the range after a range call ; after a many call the sum over its entries, however many batches it took ; after
+                                              knz_dev_read_many the distinct (source, block) pairs its reads touch */,
        KNZ_COUNTER_STAGE_BYTES0 = 8 /* 8 + i: bytes that entered transform stage i (0..7) of the last encode batch, summed over its blocks */ };
 int knz_last_counter(void* handle, int id, uint64_t* value);
 

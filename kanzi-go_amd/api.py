@@ -70,6 +70,15 @@ class _BlockRange(C.Structure):
     _fields_ = [("from_block", C.c_uint32), ("to_block", C.c_uint32), ("from_bit", C.c_uint64)]
 
 
+class _Source(C.Structure):
+    _fields_ = [("d_src", C.c_void_p), ("n", C.c_uint64), ("pos", C.POINTER(_BlockPos)), ("n_pos", C.c_uint32), ("status", C.c_int32)]
+
+
+class _Read(C.Structure):
+    _fields_ = [("source", C.c_uint32), ("reserved", C.c_uint32), ("offset", C.c_uint64), ("length", C.c_uint64), ("d_dst", C.c_void_p),
+                ("out_bytes", C.c_uint64), ("status", C.c_int32), ("reserved2", C.c_int32)]
+
+
 BLOCK_END = 0xFFFFFFFF       # KNZ_BLOCK_END: a range through the last block
 
 
@@ -122,6 +131,8 @@ def load_library(path=None):
     L.knz_dev_stream_index.argtypes = [vp, vp, C.c_uint64, C.POINTER(_StreamInfo), C.POINTER(_BlockPos), C.c_uint32, vp]
     L.knz_dev_decompress_range.argtypes = [vp, vp, C.c_uint64, C.POINTER(_BlockRange), vp, C.c_uint64, u64p, vp]
     L.knz_dev_decompress_many_range.argtypes = [vp, C.POINTER(_Stream), C.POINTER(_BlockRange), C.c_int, vp]
+    L.knz_dev_read_many.argtypes = [vp, C.POINTER(_Source), C.c_int, C.POINTER(_Read), C.c_int, vp]
+    L.knz_dev_read.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, vp, u64p, vp]
     L.knz_dev_compress_blocks.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, vp]
     L.knz_dev_decompress_blocks.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, vp]
     L.knz_dev_assemble.argtypes = [vp, C.c_int64, C.POINTER(vp), u64p, C.c_int, vp, C.c_uint64, u64p, vp]
@@ -250,6 +261,38 @@ class Codec:
         """items: [(d_src, n_bytes, d_dst, dst_cap, from_block[, to_block[, from_bit]])], entry k as dev_decompress_range of it alone, all their blocks in one
         device batch (knz_dev_decompress_many_range); the same d_src may appear in several entries. Returns [(out_bytes, status)]."""
         return self._many(self.L.knz_dev_decompress_many_range, items, check, stream, ranged=True)
+
+    def dev_read(self, d_src, n_bytes, offset, length, d_dst, stream=0):
+        """Bytes [offset, offset + length) of the decoded stream at d_src to d_dst, any alignment (knz_dev_read): only the covering blocks are decoded.
+        Returns the bytes written: fewer than length where the stream, or a short inner block, ends."""
+        out = C.c_uint64()
+        self._chk(self.L.knz_dev_read(self.h, d_src, n_bytes, offset, length, d_dst, C.byref(out), stream))
+        return out.value
+
+    def dev_read_many(self, sources, reads, check=False, stream=0):
+        """sources: [(d_src, n_bytes[, index_rows])], index_rows the [(bit, bits)] of dev_stream_index (or its first rows) as hints; reads: [(source, offset,
+        length, d_dst)]. Every distinct (source, block) the reads touch is decoded once, in one device batch (knz_dev_read_many). Returns
+        [(out_bytes, status)] per read; the call's own return value is in last_many_rc, the sources' statuses in last_source_status. Raises only with
+        check=True (the first failing read's code)."""
+        ns, nr = len(sources), len(reads)
+        src, rd, keep = (_Source * max(ns, 1))(), (_Read * max(nr, 1))(), []
+        for i, it in enumerate(sources):
+            src[i].d_src, src[i].n = it[0], it[1]
+            rows = it[2] if len(it) > 2 and it[2] else None
+            if rows:
+                pos = (_BlockPos * len(rows))()
+                for j, (bit, bits) in enumerate(rows):
+                    pos[j].bit, pos[j].bits = bit, bits
+                keep.append(pos)
+                src[i].pos, src[i].n_pos = pos, len(rows)
+        for i, (s, offset, length, d_dst) in enumerate(reads):
+            rd[i].source, rd[i].offset, rd[i].length, rd[i].d_dst = s, offset, length, d_dst
+        rc = self.L.knz_dev_read_many(self.h, src, ns, rd, nr, stream)
+        self.last_many_rc = rc
+        self.last_source_status = [int(src[i].status) for i in range(ns)]
+        if check:
+            self._chk(rc)
+        return [(int(rd[i].out_bytes), int(rd[i].status)) for i in range(nr)]
 
     def dev_compress_blocks(self, d_src, n, d_dst, dst_cap, stream=0):
         out = C.c_uint64()

@@ -26,6 +26,7 @@
 #include "bwt_sort.hip"
 #include "layout.hip"
 #include "many.hip"
+#include "read.hip"
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -355,3 +356,4 @@ extern "C" int knz_dev_compress_blocks(void* handle, const void* d_src, uint64_t
 #include "knz_host_api.inc"
 #include "knz_multi.inc"
 #include "knz_many.inc"
+#include "knz_read.inc"

@@ -104,6 +104,8 @@ struct Handle {
     DevBuf many_tab, many_blk_stream, many_blk_pos, many_heads;     // several streams in one batch (many.hip): table of streams, owner and place of every block, the streams' heads
     DevBuf many_ranges;               // ... and the table of ranges of a range call
     PinnedBuf many_pinned;            // ... the table of streams (and the heads, or the ranges) on the host
+    DevBuf read_tab, read_base;       // byte reads (read.hip): the table of reads with its entries behind it, the scan of the destination chunks
+    PinnedBuf read_pinned;            // ... the table on the host: it goes up and comes back as one copy each
     void* pinned = nullptr;           // small pinned host area for results
     // results of the last encode batch, one row per block + the batch totals behind them: packed on the device (knz_pack_results_kernel), ONE copy into pinned memory
     struct ResultRow { uint64_t written; uint64_t cksum; uint32_t post_len; int32_t status; uint32_t mode; uint32_t skip; };

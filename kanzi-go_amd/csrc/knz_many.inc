@@ -89,7 +89,15 @@ extern "C" int knz_dev_compress_many(void* handle, knz_stream* streams, int n, v
 // rg == nullptr: every stream whole, staged side by side. Else entry k's range rg[k]: the walkers read the callers' buffers, and only the bytes that hold
 // the selected frames are staged (knz_many_stage_range_kernel), so that walk, staging and batch follow the ranges and not the streams.
 // entered: the blocks of these entries that went into a decode batch (the first pass: a later one runs fewer of the same).
-static int decompress_many_once(Handle* h, knz_stream* s, const uint32_t* firstBit, const knz_block_range* rg, const knz_cfg& sc, int n, hipStream_t st, uint64_t& entered) {
+// What happens to the decoded blocks, at ostride * b in the staging buffer, is the tail's choice: rd == nullptr places them into the entries' destinations ;
+// else they are gathered into the reads of knz_dev_read_many (knz_read.inc), and the entries' d_dst / dst_cap are not looked at.
+struct ReadGather;
+struct ManyBatchView {               // what the gather tail sees of the last pass: its entries' rows (host copy) and where the blocks were decoded
+    const int* active; int A; const ManyStream* tab; const int32_t* status; uint64_t nblocks, ostride;
+};
+static int read_gather_tail(Handle* h, ReadGather& rd, const ManyBatchView& v, const knz_cfg& sc, int n, hipStream_t st);
+static int decompress_many_once(Handle* h, knz_stream* s, const uint32_t* firstBit, const knz_block_range* rg, const knz_cfg& sc, int n, hipStream_t st, uint64_t& entered,
+                                ReadGather* rd = nullptr) {
     uint64_t first_pass = 0;
     std::vector<int> active;
     std::vector<int32_t> status(n, 0);
@@ -182,6 +190,12 @@ static int decompress_many_once(Handle* h, knz_stream* s, const uint32_t* firstB
             active.swap(next);
             continue;
         }
+        if (rd) {
+            const ManyBatchView v = {active.data(), A, tab, status.data(), nblocks, ostride};
+            const int grc = read_gather_tail(h, *rd, v, sc, n, st);
+            if (grc) return grc;
+            break;
+        }
         ManyPlaceArgs p;
         p.streams = dtab; p.K = (uint32_t)A; p.blk_len = h->blk_len.as<uint32_t>(); p.blk_status = h->blk_status.as<int32_t>();
         p.blk_stream = h->many_blk_stream.as<uint32_t>(); p.blk_pos = h->many_blk_pos.as<uint64_t>(); p.stage = h->stage_out.as<uint8_t>(); p.stride = ostride;
@@ -199,20 +213,11 @@ static int decompress_many_once(Handle* h, knz_stream* s, const uint32_t* firstB
     return KNZ_OK;
 }
 
-// knz_dev_decompress_many (ranges == nullptr) and knz_dev_decompress_many_range
-static int dev_decompress_many(void* handle, knz_stream* streams, const knz_block_range* ranges, int n, void* hip_stream) {
-    if (!handle || (!streams && n > 0)) return KNZ_ERR_MISSING_PARAM;
-    if (n <= 0) return KNZ_OK;
-    Handle* h = many_begin(handle, streams, n, false);
-    DeviceGuard dg(h);
-    h->dec_blocks = 0;
-    hipStream_t st = dev_call_stream(h, hip_stream);
-    // every stream's head: one device-side gather, one copy into pinned memory; the headers are parsed here as knz_dev_decompress parses one
+// every stream's head: one device-side gather, one copy into pinned memory; the headers are parsed here as knz_dev_decompress parses one. A stream whose
+// header does not parse, or that differs from the first one that does, takes its code. KNZ_ERR_CREATE_DECOMPRESSOR: the tables could not be had.
+static int many_parse_heads(Handle* h, knz_stream* streams, int n, hipStream_t st, knz_cfg& msc, std::vector<uint32_t>& firstBit, bool& have) {
     const size_t tabBytes = sizeof(ManyStream) * (size_t)n;
-    if (h->many_pinned.reserve(tabBytes + 32 * (size_t)n) || h->many_tab.reserve(tabBytes) || h->many_heads.reserve(32 * (size_t)n)) {
-        for (int k = 0; k < n; k++) if (!streams[k].status) streams[k].status = KNZ_ERR_CREATE_DECOMPRESSOR;
-        return many_end(h, streams, n);
-    }
+    if (h->many_pinned.reserve(tabBytes + 32 * (size_t)n) || h->many_tab.reserve(tabBytes) || h->many_heads.reserve(32 * (size_t)n)) return KNZ_ERR_CREATE_DECOMPRESSOR;
     ManyStream* tab = h->many_pinned.as<ManyStream>();
     uint8_t* heads = h->many_pinned.as<uint8_t>() + tabBytes;
     for (int k = 0; k < n; k++) {
@@ -223,9 +228,6 @@ static int dev_decompress_many(void* handle, knz_stream* streams, const knz_bloc
     hipLaunchKernelGGL(knz_many_heads_kernel, dim3((n * 8 + 255) / 256), dim3(256), 0, st, (const ManyStream*)h->many_tab.as<ManyStream>(), (uint32_t)n, h->many_heads.as<uint32_t>());
     HIP_OK(hipMemcpyAsync(heads, h->many_heads.p, 32 * (size_t)n, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
-    knz_cfg msc = h->cfg;                                                 // the call's codec parameters (the first stream's) and every first block's bit
-    std::vector<uint32_t> firstBit(n, 0);
-    bool have = false;
     for (int k = 0; k < n; k++) {
         if (streams[k].status) continue;
         knz_cfg sc = h->cfg;
@@ -236,6 +238,26 @@ static int dev_decompress_many(void* handle, knz_stream* streams, const knz_bloc
         if (sc.transform != msc.transform || sc.entropy != msc.entropy || sc.block_size != msc.block_size || sc.checksum_bits != msc.checksum_bits)
             streams[k].status = KNZ_ERR_INVALID_PARAM;                    // one batch, one set of codec parameters: the first stream's
     }
+    return KNZ_OK;
+}
+
+// knz_dev_decompress_many (ranges == nullptr) and knz_dev_decompress_many_range
+static int dev_decompress_many(void* handle, knz_stream* streams, const knz_block_range* ranges, int n, void* hip_stream) {
+    if (!handle || (!streams && n > 0)) return KNZ_ERR_MISSING_PARAM;
+    if (n <= 0) return KNZ_OK;
+    Handle* h = many_begin(handle, streams, n, false);
+    DeviceGuard dg(h);
+    h->dec_blocks = 0;
+    hipStream_t st = dev_call_stream(h, hip_stream);
+    knz_cfg msc = h->cfg;                                                 // the call's codec parameters (the first stream's) and every first block's bit
+    std::vector<uint32_t> firstBit(n, 0);
+    bool have = false;
+    const int hrc = many_parse_heads(h, streams, n, st, msc, firstBit, have);
+    if (hrc == KNZ_ERR_CREATE_DECOMPRESSOR) {
+        for (int k = 0; k < n; k++) if (!streams[k].status) streams[k].status = KNZ_ERR_CREATE_DECOMPRESSOR;
+        return many_end(h, streams, n);
+    }
+    if (hrc) return hrc;
     for (int k = 0; k < n && ranges; k++)
         if (streams[k].status == 0) streams[k].status = check_block_range(h, ranges[k], streams[k].n, firstBit[k]);
     uint64_t entered = 0;                                                 // (knz_last_counter 7: over every batch of the call, halves and second passes included)
