@@ -252,6 +252,59 @@ int knz_dev_read(void* handle, const void* d_src, uint64_t n_bytes, uint64_t off
                  void* d_dst, uint64_t* out_bytes, void* hip_stream);
 
 /*
+ * Byte writes: W writes (byte offset, length, data) into ONE source stream give ONE new stream in d_dst, a WriteAt / append over .knz streams. Blocks are
+ * independent and a frame carries no block id (v2/io/CompressedStream.go:896-898, :951-976): only the blocks the writes touch are decoded and encoded
+ * again, every other frame is copied bit for bit to its new bit position, the end marker closes the stream. d_dst must not overlap d_src.
+ *   addressing: as knz_dev_read_many: byte `offset` lies in block offset / block_size + 1. The old length L = (n_blocks - 1) * block_size + the decoded
+ *               length of the last block (0 for a stream of header + end marker). L is needed only when a write reaches the last block (its end lies behind
+ *               (n_blocks - 1) * block_size) or uses KNZ_OFFSET_END: the last block then counts as touched, whether a byte of it changes or not.
+ *   order:      the writes apply in index order: where two overlap the later one wins. KNZ_OFFSET_END resolves to the length of the stream as it stands
+ *               when that write is applied, the growth of earlier writes included. A write whose resolved offset lies behind that length would leave a
+ *               hole: KNZ_ERR_INVALID_PARAM on that write. A write may run past the end: the new length L' = max(L, every write's end), the new stream
+ *               has ceil(L' / block_size) blocks.
+ *   all or nothing: the result is one stream, so a failing write fails the call: it returns the code of the first failing write (lowest index),
+ *               *out_bytes = 0 and NO byte of d_dst is written. Every writes[i].status is set: a write's own code (its arguments, a hole, the code of
+ *               the first failing block it touches; 0 for a write that is not to blame), or, where the call fails for a reason that is no write's
+ *               (the source's header or framing, the configuration, dst_cap, the workspace), that code on every write. Argument errors are reported
+ *               before the stream is looked at: holes are then not looked for.
+ *   touched:    a block is touched when some write covers one of its bytes (visible or overwritten by a later write), or when it is new. Every touched
+ *               existing block is decoded and checksum-verified, all of them in one decode batch (entries of one block each, as knz_dev_read_many's);
+ *               the visible bytes of the writes are laid over them; all touched blocks, existing and new, are encoded in one encode batch under the
+ *               handle's knz_cfg. A touched block that fails to decode fails the call with the code knz_dev_decompress_range gives for that block
+ *               alone. A touched block that is not the last one and decodes to fewer than block_size bytes is a short inner block: its offsets are not
+ *               those of the decoded stream, KNZ_ERR_INVALID_PARAM.
+ *   untouched:  frames no write touches are never decoded or checked: their bits (framing field and payload) are copied verbatim, damaged payloads and
+ *               short inner blocks included. The framing is walked from the header to the end marker: damaged framing anywhere fails the call with
+ *               the code knz_dev_stream_index gives for the stream.
+ *   configuration: the source header's transform, entropy codec, block size and checksum size must equal the handle's knz_cfg, else
+ *               KNZ_ERR_INVALID_PARAM. Hence, for a source written under this configuration and these flags, d_dst[0 .. out_bytes) equals byte for
+ *               byte what knz_dev_compress writes for the edited input with the same header_input_size.
+ *   header:     rebuilt by the function knz_dev_compress uses; header_input_size means what it means there (0 = no size field).
+ *               KNZ_HEADER_SIZE_KEEP: no field if the source has none, else the source's value + (L' - L). The header is 0, 16, 32 or 48 bits longer
+ *               with the field (:466-490): another field shifts every frame.
+ *   dst_cap:    the single calls' rule: whole big-endian words are stored, the stream plus up to 7 bytes must fit. Checked on the device before any
+ *               word is stored; too small: KNZ_ERR_WRITE_FILE, nothing is written. After a good call nothing behind the stream's last word is written.
+ *   arguments:  n_writes <= 0: returns 0, *out_bytes = 0, nothing is written. NULL writes, d_src, d_dst or out_bytes: KNZ_ERR_MISSING_PARAM. d_src or d_dst
+ *               off 4 bytes: KNZ_ERR_INVALID_PARAM. A NULL d_data with length > 0: KNZ_ERR_MISSING_PARAM on that write; offset + length overflowing:
+ *               KNZ_ERR_INVALID_PARAM on that write. d_data may have any alignment.
+ *   workspace:  on a handle of several lanes the call runs on the lane that owns d_dst. A decode or encode batch whose workspace the device refuses
+ *               is taken in halves (the many calls' rule) ; the touched blocks and their streams themselves have to fit.
+ *   counters:   KNZ_COUNTER_DECODE_BATCH_BLOCKS: the touched existing blocks ; KNZ_COUNTER_ENCODE_BATCH_BLOCKS: those and the new ones.
+ *   knz_dev_append: one write at KNZ_OFFSET_END (length 0: the stream comes back under the new header).
+ */
+#define KNZ_OFFSET_END  0xFFFFFFFFFFFFFFFFull    /* "at the end of the decoded stream as it stands when this write is applied" */
+#define KNZ_HEADER_SIZE_KEEP (-1)                /* header size field: none if the source has none, else the source's value + (new length - old length) */
+typedef struct {
+    uint64_t offset, length;   /* bytes of the decoded stream; offset may be KNZ_OFFSET_END */
+    const void* d_data;        /* device, ANY alignment, `length` bytes readable */
+    int32_t status, reserved;  /* result */
+} knz_write;
+int knz_dev_write_many(void* handle, const void* d_src, uint64_t n_bytes, knz_write* writes, int n_writes,
+                       int64_t header_input_size, void* d_dst, uint64_t dst_cap, uint64_t* out_bytes, void* hip_stream);
+int knz_dev_append(void* handle, const void* d_src, uint64_t n_bytes, const void* d_data, uint64_t length,
+                   int64_t header_input_size, void* d_dst, uint64_t dst_cap, uint64_t* out_bytes, void* hip_stream);
+
+/*
  * Multi-GPU block sharding: a rank encodes blocks [first_block, first_block+n_blocks) of a
  * stream whose blocks are block_size bytes each; d_src points at this rank's first block. The result is a
  * bit string (no stream header, no end marker): *out_bits bits, zero padded to a byte in d_dst.
@@ -305,7 +358,8 @@ enum { KNZ_COUNTER_HUF_SERIAL_CHUNKS = 0, KNZ_COUNTER_POST_TRANSFORM_BYTES = 1 /
        KNZ_COUNTER_DECODE_BATCH_BLOCKS = 7 /* blocks that entered the last decode batch: a stream's block count after knz_dev_decompress, the blocks of
                                               the range after a range call ; after a many call the sum over its entries, however many batches it took ; after
                                               knz_dev_read_many the distinct (source, block) pairs its reads touch */,
-       KNZ_COUNTER_STAGE_BYTES0 = 8 /* 8 + i: bytes that entered transform stage i (0..7) of the last encode batch, summed over its blocks */ };
+       KNZ_COUNTER_STAGE_BYTES0 = 8 /* 8 + i: bytes that entered transform stage i (0..7) of the last encode batch, summed over its blocks */,
+       KNZ_COUNTER_ENCODE_BATCH_BLOCKS = 16 /* blocks that entered the encode batch of the last knz_dev_write_many / knz_dev_append: the touched and the new ones */ };
 int knz_last_counter(void* handle, int id, uint64_t* value);
 
 /* 1 when a transform/entropy id has a device implementation in this build */

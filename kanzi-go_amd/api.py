@@ -79,7 +79,13 @@ class _Read(C.Structure):
                 ("out_bytes", C.c_uint64), ("status", C.c_int32), ("reserved2", C.c_int32)]
 
 
+class _Write(C.Structure):
+    _fields_ = [("offset", C.c_uint64), ("length", C.c_uint64), ("d_data", C.c_void_p), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
 BLOCK_END = 0xFFFFFFFF       # KNZ_BLOCK_END: a range through the last block
+OFFSET_END = 0xFFFFFFFFFFFFFFFF   # KNZ_OFFSET_END: a write at the end of the decoded stream as it stands when the write is applied
+HEADER_SIZE_KEEP = -1        # KNZ_HEADER_SIZE_KEEP: the source's size field, moved by the growth
 
 
 def library_path():
@@ -133,6 +139,8 @@ def load_library(path=None):
     L.knz_dev_decompress_many_range.argtypes = [vp, C.POINTER(_Stream), C.POINTER(_BlockRange), C.c_int, vp]
     L.knz_dev_read_many.argtypes = [vp, C.POINTER(_Source), C.c_int, C.POINTER(_Read), C.c_int, vp]
     L.knz_dev_read.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, vp, u64p, vp]
+    L.knz_dev_write_many.argtypes = [vp, vp, C.c_uint64, C.POINTER(_Write), C.c_int, C.c_int64, vp, C.c_uint64, u64p, vp]
+    L.knz_dev_append.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.c_int64, vp, C.c_uint64, u64p, vp]
     L.knz_dev_compress_blocks.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, vp]
     L.knz_dev_decompress_blocks.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, vp]
     L.knz_dev_assemble.argtypes = [vp, C.c_int64, C.POINTER(vp), u64p, C.c_int, vp, C.c_uint64, u64p, vp]
@@ -293,6 +301,32 @@ class Codec:
         if check:
             self._chk(rc)
         return [(int(rd[i].out_bytes), int(rd[i].status)) for i in range(nr)]
+
+    def dev_write_many(self, d_src, n_bytes, writes, d_dst, dst_cap, header_input_size=HEADER_SIZE_KEEP, check=False, stream=0):
+        """writes: [(offset, length, d_data)], bytes of the decoded stream at d_src (offset may be OFFSET_END), applied in order; the new stream goes to
+        d_dst (knz_dev_write_many): only the blocks the writes touch are decoded and encoded again, every other frame is copied bit for bit. Returns
+        (out_bytes, [status] per write); the call's own return value is in last_many_rc. All or nothing: a failing write fails the call, out_bytes is 0
+        and d_dst is untouched. Raises only with check=True."""
+        n = len(writes)
+        arr = (_Write * max(n, 1))()
+        for i, (offset, length, d_data) in enumerate(writes):
+            arr[i].offset, arr[i].length, arr[i].d_data = offset, length, d_data
+        out = C.c_uint64()
+        rc = self.L.knz_dev_write_many(self.h, d_src, n_bytes, arr, n, header_input_size, d_dst, dst_cap, C.byref(out), stream)
+        self.last_many_rc = rc
+        if check:
+            self._chk(rc)
+        return out.value, [int(arr[i].status) for i in range(n)]
+
+    def dev_append(self, d_src, n_bytes, d_data, length, d_dst, dst_cap, header_input_size=HEADER_SIZE_KEEP, check=False, stream=0):
+        """length bytes at d_data behind the end of the decoded stream at d_src, the new stream to d_dst (knz_dev_append). Returns out_bytes (0 where the
+        call fails); the return value is in last_many_rc. Raises only with check=True."""
+        out = C.c_uint64()
+        rc = self.L.knz_dev_append(self.h, d_src, n_bytes, d_data, length, header_input_size, d_dst, dst_cap, C.byref(out), stream)
+        self.last_many_rc = rc
+        if check:
+            self._chk(rc)
+        return out.value
 
     def dev_compress_blocks(self, d_src, n, d_dst, dst_cap, stream=0):
         out = C.c_uint64()

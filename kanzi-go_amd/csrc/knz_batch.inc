@@ -11,6 +11,7 @@ struct EncodeBatch {
     int framed = 0, with_header = 0, with_end = 0; int64_t header_input_size = 0;
     uint64_t out_stride = 0; // framed == 0
     int payload_only = 0;    // 1: single EntropyEncoder object, no block header bits
+    int keep_probes = 0;     // 1: the kernel probes of the call so far stay, this batch's follow them (knz_dev_write_many: its overlay runs in front)
     uint64_t total_bits = 0; // result
     // several streams in one batch (knz_many.inc; on block_streams): the blocks are those of a table of streams, `blocks` of them, none longer than
     // max_len; a block that fails leaves its status in blk_status for the caller instead of failing the batch
@@ -465,7 +466,7 @@ __global__ void knz_pack_results_kernel(uint32_t nblocks, const uint64_t* writte
 
 static int encode_batch(Handle* h, EncodeBatch& eb, hipStream_t st) {
     const knz_cfg& cfg = h->cfg;
-    h->nprobes = 0;
+    if (!eb.keep_probes) h->nprobes = 0;
     if (!knz_supports(cfg.transform, cfg.entropy))
         return knz_set_error(h, KNZ_ERR_INVALID_CODEC, "transform/entropy combination has no device implementation in this build");
     const EntropyCodec& ec = *entropy_codec(cfg.entropy);

@@ -27,6 +27,7 @@
 #include "layout.hip"
 #include "many.hip"
 #include "read.hip"
+#include "write.hip"
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -287,12 +288,13 @@ static int sum_flags(const DevBuf& buf, size_t n, uint8_t only, uint64_t* value)
 
 extern "C" int knz_last_counter(void* handle, int id, uint64_t* value) {
     Handle* h = (Handle*)handle;
-    if (!h || !value || id < KNZ_COUNTER_HUF_SERIAL_CHUNKS || id > KNZ_COUNTER_STAGE_BYTES0 + 7) return KNZ_ERR_INVALID_PARAM;
+    if (!h || !value || id < KNZ_COUNTER_HUF_SERIAL_CHUNKS || id > KNZ_COUNTER_ENCODE_BATCH_BLOCKS) return KNZ_ERR_INVALID_PARAM;
     if (h->multi) return multi_last_counter(h, id, value);
     DeviceGuard dg(h);
     *value = 0;
     if (id == KNZ_COUNTER_POST_TRANSFORM_BYTES) { *value = h->post_bytes; return KNZ_OK; }
     if (id == KNZ_COUNTER_DECODE_BATCH_BLOCKS) { *value = h->dec_blocks; return KNZ_OK; }
+    if (id == KNZ_COUNTER_ENCODE_BATCH_BLOCKS) { *value = h->enc_blocks; return KNZ_OK; }
     if (id >= KNZ_COUNTER_STAGE_BYTES0) { *value = h->stage_bytes[id - KNZ_COUNTER_STAGE_BYTES0]; return KNZ_OK; }
     if (id == KNZ_COUNTER_TEXT_CHAIN_BLOCKS) {
         uint32_t v = 0;
@@ -357,3 +359,4 @@ extern "C" int knz_dev_compress_blocks(void* handle, const void* d_src, uint64_t
 #include "knz_multi.inc"
 #include "knz_many.inc"
 #include "knz_read.inc"
+#include "knz_write.inc"

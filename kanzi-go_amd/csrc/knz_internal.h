@@ -3,6 +3,7 @@
 #pragma once
 #include "../../include/knz_gpu.h"
 #include "bits.h"
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -51,6 +52,10 @@ struct PinnedBuf {
 #define KNZ_MAX_PROBES 128
 struct KernelProbe { const char* name = nullptr; hipEvent_t a = nullptr, b = nullptr; };
 
+// Byte writes (knz_write.inc): the touched blocks at a stride of one block size, their block-local streams, the tables of the overlay and the splice.
+// Not part of the handle's workspace list: a workspace given back between the halves of a refused batch must not take the decoded blocks with it.
+struct WriteBufs { DevBuf blocks, streams, tab; PinnedBuf pinned; };
+
 struct MultiDev;                      // several lanes (devices, or streams of one device) behind one handle: knz_multi.inc
 
 struct Handle {
@@ -61,6 +66,8 @@ struct Handle {
     uint64_t stage_bytes[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // bytes that entered transform stage i of the last encode batch (knz_last_counter 8 + i)
     DevBuf stage_sum;                 // their device-side sums
     uint64_t dec_blocks = 0;          // blocks that entered the last decode batch (knz_last_counter 7)
+    uint64_t enc_blocks = 0;          // blocks that entered the last encode batch of knz_dev_write_many (knz_last_counter 16)
+    std::unique_ptr<WriteBufs> wr;    // ... its buffers, made by the first such call
     uint64_t post_bytes = 0;          // bytes behind the transform sequence of the last encode batch (entropy coder input)
     int device = 0;
     hipStream_t stream = nullptr;
