@@ -305,6 +305,63 @@ int knz_dev_append(void* handle, const void* d_src, uint64_t n_bytes, const void
                    int64_t header_input_size, void* d_dst, uint64_t dst_cap, uint64_t* out_bytes, void* hip_stream);
 
 /*
+ * Block splice: parts (source stream, block range) become output streams, and nothing but whole frames moves. Blocks are independent, a frame carries no
+ * block id, the checksum travels inside the frame and the header does not depend on the block count: concatenating K streams, slicing blocks [from, to)
+ * out of one, splitting one into K or regrouping any list of parts into any number of outputs needs no decode chain and no encode chain.
+ *   result:     output o holds the header, then the frames of its parts in part order, then the end marker. Every frame is bit for bit the source's:
+ *               framing field and payload, copy blocks, skip flags, checksums and damaged payloads included. Nothing is decoded, encoded or
+ *               checksum-verified: KNZ_COUNTER_DECODE_BATCH_BLOCKS and KNZ_COUNTER_ENCODE_BATCH_BLOCKS read 0 after the call.
+ *   identity:   for whole streams whose decoded lengths, except the last one's, are multiples of the block size, the output equals byte for byte what
+ *               knz_dev_compress writes for the concatenated input under that header size.
+ *   ranges:     mean what knz_dev_decompress_range's mean (ids from 1, to exclusive, KNZ_BLOCK_END = through the last block). from_block == 0 or
+ *               to_block <= from_block: KNZ_ERR_INVALID_PARAM on that part. to_block is clamped to the last block ; a range wholly behind the last
+ *               block contributes nothing (status 0, blocks 0). With a finite to_block the framing behind the range is not read: damage there does
+ *               not fail the part. With KNZ_BLOCK_END the walk runs to the end marker and checks it. Damaged framing in front of the range or inside
+ *               it gives the code knz_dev_stream_index gives for that stream. A stream of header + end marker is a valid, empty part; an output with no
+ *               parts, or only empty ones, is header + end marker. Each distinct (d_src, n_bytes) of the call is walked once, from its header to the
+ *               largest boundary some part asks for, however many parts and outputs name it.
+ *   configuration: every source's transform, entropy codec, block size and checksum size must equal the handle's knz_cfg (the write call's rule), else
+ *               KNZ_ERR_INVALID_PARAM on the part ; a header that does not parse gives its code. The header is rebuilt by the function
+ *               knz_dev_compress uses ; header_input_size means what it means there (0 = no size field). KNZ_HEADER_SIZE_KEEP: the sum of the sources'
+ *               size fields when every part of the output is a whole stream ({1, KNZ_BLOCK_END}) and every such source has the field, else no field.
+ *   short inner blocks: a part whose last block is short, followed by another part, gives a short inner block. That is still a valid stream:
+ *               knz_dev_decompress and the reference Reader return the concatenation. The byte addressing of knz_dev_read_many and knz_dev_write_many
+ *               behind such a block is off, as their own text says. The splice cannot know: it does not decode.
+ *   failure:    per output. An output fails with its own pointer code (NULL d_dst: KNZ_ERR_MISSING_PARAM ; d_dst off 4 bytes, on another device than the
+ *               call's lane, or d_dst[0 .. dst_cap) overlapping a source of the call or another output's range, checked on the host from the pointers:
+ *               KNZ_ERR_INVALID_PARAM), else with the code of its first failing part (lowest index ; a NULL d_src: KNZ_ERR_MISSING_PARAM, a d_src off
+ *               4 bytes: KNZ_ERR_INVALID_PARAM, its header's, configuration's, range's or walk's code), else with KNZ_ERR_WRITE_FILE for a dst_cap
+ *               too small. dst_cap follows the single calls' rule (whole big-endian words are stored, the stream plus up to 7 bytes must fit) and is
+ *               checked on the device before any store. A failed output has out_bytes 0 and NO byte of its d_dst is written ; the other outputs
+ *               complete. After a good output nothing behind the stream's last 32-bit word is written. The call returns 0 or the status of the first
+ *               failed output (lowest index).
+ *   arguments:  n_outs <= 0 returns 0 ; n_parts may be 0. NULL outs, or NULL parts with n_parts > 0: KNZ_ERR_MISSING_PARAM. Parts of one output are
+ *               consecutive and in output order: an `out` that is out of range or decreases gives KNZ_ERR_INVALID_PARAM for the call (every output's
+ *               status), and nothing is written. The same d_src may appear in any number of parts and outputs.
+ *   lanes:      on a handle of several lanes the call runs on the lane that owns outs[0].d_dst.
+ *   safety:     whatever a stream says, every read stays inside its own d_src[0 .. n_bytes) rounded up to 4 and every write inside its output's dst_cap.
+ *   knz_dev_concat: n whole streams -> one (n <= 0: header + end marker). knz_dev_slice: one range -> one stream. Both are knz_dev_splice_many with one output.
+ */
+typedef struct {
+    const void* d_src; uint64_t n_bytes;  /* one .knz stream, device, 4-byte aligned, readable to the next multiple of 4 */
+    uint32_t from_block, to_block;        /* ids from 1, to exclusive, KNZ_BLOCK_END = through the last block (knz_block_range's meaning) */
+    uint32_t out;                         /* index into outs[]; parts of one output are consecutive and in output order: out is non-decreasing */
+    int32_t  status;                      /* result */
+    uint64_t blocks, bits;                /* result: frames taken from this part, and their bits */
+} knz_splice_part;
+typedef struct {
+    void* d_dst; uint64_t dst_cap;        /* 4-byte aligned; the single calls' rule for dst_cap */
+    int64_t header_input_size;            /* as knz_dev_compress (0 = no field), or KNZ_HEADER_SIZE_KEEP */
+    uint64_t out_bytes, out_blocks;       /* result */
+    int32_t status, reserved;             /* result */
+} knz_splice_out;
+int knz_dev_splice_many(void* handle, knz_splice_part* parts, int n_parts, knz_splice_out* outs, int n_outs, void* hip_stream);
+int knz_dev_concat(void* handle, const void* const* d_srcs, const uint64_t* n_bytes, int n, int64_t header_input_size,
+                   void* d_dst, uint64_t dst_cap, uint64_t* out_bytes, void* hip_stream);
+int knz_dev_slice(void* handle, const void* d_src, uint64_t n_bytes, uint32_t from_block, uint32_t to_block, int64_t header_input_size,
+                  void* d_dst, uint64_t dst_cap, uint64_t* out_bytes, void* hip_stream);
+
+/*
  * Multi-GPU block sharding: a rank encodes blocks [first_block, first_block+n_blocks) of a
  * stream whose blocks are block_size bytes each; d_src points at this rank's first block. The result is a
  * bit string (no stream header, no end marker): *out_bits bits, zero padded to a byte in d_dst.

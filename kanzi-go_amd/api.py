@@ -83,9 +83,19 @@ class _Write(C.Structure):
     _fields_ = [("offset", C.c_uint64), ("length", C.c_uint64), ("d_data", C.c_void_p), ("status", C.c_int32), ("reserved", C.c_int32)]
 
 
+class _SplicePart(C.Structure):
+    _fields_ = [("d_src", C.c_void_p), ("n_bytes", C.c_uint64), ("from_block", C.c_uint32), ("to_block", C.c_uint32), ("out", C.c_uint32),
+                ("status", C.c_int32), ("blocks", C.c_uint64), ("bits", C.c_uint64)]
+
+
+class _SpliceOut(C.Structure):
+    _fields_ = [("d_dst", C.c_void_p), ("dst_cap", C.c_uint64), ("header_input_size", C.c_int64), ("out_bytes", C.c_uint64), ("out_blocks", C.c_uint64),
+                ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
 BLOCK_END = 0xFFFFFFFF       # KNZ_BLOCK_END: a range through the last block
 OFFSET_END = 0xFFFFFFFFFFFFFFFF   # KNZ_OFFSET_END: a write at the end of the decoded stream as it stands when the write is applied
-HEADER_SIZE_KEEP = -1        # KNZ_HEADER_SIZE_KEEP: the source's size field, moved by the growth
+HEADER_SIZE_KEEP = -1        # KNZ_HEADER_SIZE_KEEP: the source's size field, moved by the growth (splice: the sum of the whole sources' fields)
 
 
 def library_path():
@@ -141,6 +151,9 @@ def load_library(path=None):
     L.knz_dev_read.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, vp, u64p, vp]
     L.knz_dev_write_many.argtypes = [vp, vp, C.c_uint64, C.POINTER(_Write), C.c_int, C.c_int64, vp, C.c_uint64, u64p, vp]
     L.knz_dev_append.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.c_int64, vp, C.c_uint64, u64p, vp]
+    L.knz_dev_splice_many.argtypes = [vp, C.POINTER(_SplicePart), C.c_int, C.POINTER(_SpliceOut), C.c_int, vp]
+    L.knz_dev_concat.argtypes = [vp, C.POINTER(vp), u64p, C.c_int, C.c_int64, vp, C.c_uint64, u64p, vp]
+    L.knz_dev_slice.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int64, vp, C.c_uint64, u64p, vp]
     L.knz_dev_compress_blocks.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, vp]
     L.knz_dev_decompress_blocks.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, vp]
     L.knz_dev_assemble.argtypes = [vp, C.c_int64, C.POINTER(vp), u64p, C.c_int, vp, C.c_uint64, u64p, vp]
@@ -323,6 +336,51 @@ class Codec:
         call fails); the return value is in last_many_rc. Raises only with check=True."""
         out = C.c_uint64()
         rc = self.L.knz_dev_append(self.h, d_src, n_bytes, d_data, length, header_input_size, d_dst, dst_cap, C.byref(out), stream)
+        self.last_many_rc = rc
+        if check:
+            self._chk(rc)
+        return out.value
+
+    def dev_splice_many(self, parts, outs, check=False, stream=0):
+        """parts: [(d_src, n_bytes, from_block, to_block, out)], blocks from_block .. to_block - 1 (ids from 1; to_block None: through the last) of the stream at
+        d_src go to output `out`; the parts of one output are consecutive and in output order. outs: [(d_dst, dst_cap[, header_input_size])], the header
+        size as dev_compress's (0: no field; default HEADER_SIZE_KEEP). Whole frames move bit for bit, nothing is decoded or encoded
+        (knz_dev_splice_many). Returns ([(out_bytes, out_blocks, status)] per output, [(blocks, bits, status)] per part); the call's own return value
+        is in last_many_rc. A failed output has out_bytes 0 and its d_dst untouched, the others complete. Raises only with check=True."""
+        n, m = len(parts), len(outs)
+        pa, oa = (_SplicePart * max(n, 1))(), (_SpliceOut * max(m, 1))()
+        for i, (d_src, n_bytes, from_block, to_block, out) in enumerate(parts):
+            pa[i].d_src, pa[i].n_bytes, pa[i].from_block, pa[i].out = d_src, n_bytes, from_block, out
+            pa[i].to_block = BLOCK_END if to_block is None else to_block
+        for i, it in enumerate(outs):
+            oa[i].d_dst, oa[i].dst_cap = it[0], it[1]
+            oa[i].header_input_size = it[2] if len(it) > 2 and it[2] is not None else HEADER_SIZE_KEEP
+        rc = self.L.knz_dev_splice_many(self.h, pa, n, oa, m, stream)
+        self.last_many_rc = rc
+        if check:
+            self._chk(rc)
+        return ([(int(oa[i].out_bytes), int(oa[i].out_blocks), int(oa[i].status)) for i in range(m)],
+                [(int(pa[i].blocks), int(pa[i].bits), int(pa[i].status)) for i in range(n)])
+
+    def dev_concat(self, d_srcs, n_bytes, d_dst, dst_cap, header_input_size=HEADER_SIZE_KEEP, check=False, stream=0):
+        """The whole streams at d_srcs[i] (n_bytes[i] bytes each), in order, as one stream at d_dst (knz_dev_concat). Returns out_bytes (0 where the call
+        fails); the return value is in last_many_rc. Raises only with check=True."""
+        n = len(d_srcs)
+        srcs = (C.c_void_p * max(n, 1))(*d_srcs)
+        lens = (C.c_uint64 * max(n, 1))(*n_bytes)
+        out = C.c_uint64()
+        rc = self.L.knz_dev_concat(self.h, srcs, lens, n, header_input_size, d_dst, dst_cap, C.byref(out), stream)
+        self.last_many_rc = rc
+        if check:
+            self._chk(rc)
+        return out.value
+
+    def dev_slice(self, d_src, n_bytes, from_block, to_block, d_dst, dst_cap, header_input_size=HEADER_SIZE_KEEP, check=False, stream=0):
+        """Blocks from_block .. to_block - 1 (to_block None: through the last) of the stream at d_src as a stream of their own at d_dst (knz_dev_slice).
+        Returns out_bytes (0 where the call fails); the return value is in last_many_rc. Raises only with check=True."""
+        out = C.c_uint64()
+        rc = self.L.knz_dev_slice(self.h, d_src, n_bytes, from_block, BLOCK_END if to_block is None else to_block, header_input_size, d_dst, dst_cap,
+                                  C.byref(out), stream)
         self.last_many_rc = rc
         if check:
             self._chk(rc)

@@ -28,6 +28,7 @@
 #include "many.hip"
 #include "read.hip"
 #include "write.hip"
+#include "splice.hip"
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -360,3 +361,4 @@ extern "C" int knz_dev_compress_blocks(void* handle, const void* d_src, uint64_t
 #include "knz_many.inc"
 #include "knz_read.inc"
 #include "knz_write.inc"
+#include "knz_splice.inc"
