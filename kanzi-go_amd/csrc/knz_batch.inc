@@ -333,7 +333,7 @@ static int ans1_decode_stage(Handle* h, DecStage& d, hipStream_t st) {
     Ans1DecArgs da;
     dec_io(da, d.db, h, d.cpb); da.nslots = ns;
     da.dtab = h->a1_dtab.as<uint32_t>(); da.info = h->a1_info.as<uint32_t>(); da.paybit = h->a1_paybit.as<uint64_t>();
-    da.plain_loop = knz_test_switch("KNZ_ANS1_PLAIN") != nullptr ? 1u : (knz_test_switch("KNZ_ANS1_LOHI_LDS") != nullptr ? 2u : 0u);
+    da.plain_loop = knz_test_switch("KNZ_ANS1_PLAIN") != nullptr ? 1u : (knz_test_switch("KNZ_ANS1_LOHI_LDS") != nullptr ? 2u : (knz_test_switch("KNZ_ANS1_R5_LOOP") != nullptr ? 3u : 0u));
     // The LDS decoder (cumulated frequencies of a chunk's 256 contexts in 129 KiB of LDS: one chunk per CU at a time, ~100-165 ms per 4 MiB chunk)
     // takes a batch of any size in ONE launch: the hardware hands a CU the next chunk as soon as one ends. The HBM-table decoder (2 MiB of slot
     // tables per chunk, 16 chunks per wave) is flat at ~830-880 ms up to thousands of chunks: measured crossover (profiles/r04_saturation_*.json,
