@@ -252,6 +252,50 @@ int knz_dev_read(void* handle, const void* d_src, uint64_t n_bytes, uint64_t off
                  void* d_dst, uint64_t* out_bytes, void* hip_stream);
 
 /*
+ * Pattern search: Q queries (source, window, byte string) give the decoded offsets at which the string starts, a bytes.find / zgrep over .knz streams. The
+ * covering blocks are decoded once, in one batch, and searched where they lie in the workspace: no decoded byte reaches the caller, only offsets do.
+ * Where nothing else is said a query behaves like the read (offset, length + pattern_len - 1) of knz_dev_read_many, its EXTENDED READ.
+ *   addressing: as knz_dev_read_many: byte `offset` lies in block offset / block_size + 1 at offset % block_size. Let ext be the bytes the extended read
+ *               would deliver: it stops at the end of a block that decoded to fewer than block_size bytes (the stream's last block, or a short inner
+ *               block). scanned = min(length, ext). A match is a position p in [offset, offset + scanned) with p - offset + pattern_len <= ext and
+ *               the decoded bytes at p .. equal to the pattern: it STARTS inside the window and may end behind the window's end; one that starts
+ *               in front of the window is none. Overlapping matches all count: "aaa" in "aaaaa" gives 3.
+ *   results:    n_hits is the number of matches and is not clipped. d_hits[0 .. min(n_hits, hits_cap)) holds their absolute decoded offsets in
+ *               ascending order, nothing behind that is written (8-byte stores). The same input gives the same words on every run.
+ *   once:       every distinct (source, block) pair that some query touches is decoded once, however many queries and patterns name it;
+ *               KNZ_COUNTER_DECODE_BATCH_BLOCKS reports that number.
+ *   locality:   a query's result depends only on its own source, window and pattern. A failing block inside the extended read's window fails the
+ *               query with that block's code (knz_dev_decompress_range's for that block alone): n_hits = 0 and NOTHING of its d_hits is written.
+ *               Queries over other blocks of the same stream complete.
+ *   no phantom entries: no entry of the batch is made for a block that does not exist. KNZ_LENGTH_END, and windows far past the end, are clamped
+ *               to the source's block count, taken from ONE framing walk per queried source (knz_dev_stream_index's walk, up to the last block a
+ *               query of the call asks for). Where that walk meets damaged framing, the blocks in front of the damage count: queries inside them
+ *               complete, a query that reaches the frame the walk could not read, or lies behind it, fails with the walk's code (as a read there does). Hints (pos / n_pos) mean what they mean for reads; the count walk
+ *               starts at the last hinted frame, and is not run where the hints cover every block the queries ask for.
+ *   arguments:  pattern_len 0 or above KNZ_FIND_MAX_PATTERN, source >= n_sources, offset + length overflowing (length not KNZ_LENGTH_END), d_hits off
+ *               8 bytes: KNZ_ERR_INVALID_PARAM on the query. NULL pattern, NULL d_hits with hits_cap > 0: KNZ_ERR_MISSING_PARAM on the query. A
+ *               source's non-zero status (knz_dev_read_many's rules) is the status of its queries. length == 0, or an offset at or behind the end:
+ *               status 0, n_hits = 0, scanned = 0. NULL finds or sources (n_finds > 0): the call returns KNZ_ERR_MISSING_PARAM. n_finds <= 0
+ *               returns 0. The call returns 0 or the status of the first query (lowest index) that failed.
+ *   workspace:  a query list whose workspace the device refuses is taken in halves, as reads are; one query's window has to fit. On a handle of
+ *               several lanes the call runs on the lane that owns finds[0].d_hits, else on the first lane.
+ *   knz_dev_find: one source, its whole stream ({0, KNZ_LENGTH_END}), no hint. n_hits is a host pointer.
+ */
+#define KNZ_FIND_MAX_PATTERN 256
+#define KNZ_LENGTH_END 0xFFFFFFFFFFFFFFFFull      /* window runs to the end of the stream */
+typedef struct {
+    uint32_t source, pattern_len;       /* index into sources[]; 1 .. KNZ_FIND_MAX_PATTERN */
+    const void* pattern;                /* HOST, pattern_len bytes */
+    uint64_t offset, length;            /* matches that START in [offset, offset + length) of the decoded stream */
+    uint64_t* d_hits; uint64_t hits_cap;/* device, 8-byte aligned, may be NULL when hits_cap == 0 (count only) */
+    uint64_t n_hits, scanned;           /* results */
+    int32_t  status, reserved;          /* result */
+} knz_find;
+int knz_dev_find_many(void* handle, knz_source* sources, int n_sources, knz_find* finds, int n_finds, void* hip_stream);
+int knz_dev_find(void* handle, const void* d_src, uint64_t n_bytes, const void* pattern, uint32_t pattern_len,
+                 uint64_t* d_hits, uint64_t hits_cap, uint64_t* n_hits, void* hip_stream);   /* one source, whole stream */
+
+/*
  * Byte writes: W writes (byte offset, length, data) into ONE source stream give ONE new stream in d_dst, a WriteAt / append over .knz streams. Blocks are
  * independent and a frame carries no block id (v2/io/CompressedStream.go:896-898, :951-976): only the blocks the writes touch are decoded and encoded
  * again, every other frame is copied bit for bit to its new bit position, the end marker closes the stream. d_dst must not overlap d_src.
@@ -414,7 +458,7 @@ enum { KNZ_COUNTER_HUF_SERIAL_CHUNKS = 0, KNZ_COUNTER_POST_TRANSFORM_BYTES = 1 /
        KNZ_COUNTER_RANK_PIPE_BLOCKS = 6 /* blocks of the last decode batch whose ZRLT / RANK inverses ran as one chain under the order-1 rANS decoder */,
        KNZ_COUNTER_DECODE_BATCH_BLOCKS = 7 /* blocks that entered the last decode batch: a stream's block count after knz_dev_decompress, the blocks of
                                               the range after a range call ; after a many call the sum over its entries, however many batches it took ; after
-                                              knz_dev_read_many the distinct (source, block) pairs its reads touch */,
+                                              knz_dev_read_many / knz_dev_find_many the distinct (source, block) pairs its reads / queries touch */,
        KNZ_COUNTER_STAGE_BYTES0 = 8 /* 8 + i: bytes that entered transform stage i (0..7) of the last encode batch, summed over its blocks */,
        KNZ_COUNTER_ENCODE_BATCH_BLOCKS = 16 /* blocks that entered the encode batch of the last knz_dev_write_many / knz_dev_append: the touched and the new ones */ };
 int knz_last_counter(void* handle, int id, uint64_t* value);

@@ -79,6 +79,11 @@ class _Read(C.Structure):
                 ("out_bytes", C.c_uint64), ("status", C.c_int32), ("reserved2", C.c_int32)]
 
 
+class _Find(C.Structure):
+    _fields_ = [("source", C.c_uint32), ("pattern_len", C.c_uint32), ("pattern", C.c_void_p), ("offset", C.c_uint64), ("length", C.c_uint64),
+                ("d_hits", C.c_void_p), ("hits_cap", C.c_uint64), ("n_hits", C.c_uint64), ("scanned", C.c_uint64), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
 class _Write(C.Structure):
     _fields_ = [("offset", C.c_uint64), ("length", C.c_uint64), ("d_data", C.c_void_p), ("status", C.c_int32), ("reserved", C.c_int32)]
 
@@ -95,6 +100,8 @@ class _SpliceOut(C.Structure):
 
 BLOCK_END = 0xFFFFFFFF       # KNZ_BLOCK_END: a range through the last block
 OFFSET_END = 0xFFFFFFFFFFFFFFFF   # KNZ_OFFSET_END: a write at the end of the decoded stream as it stands when the write is applied
+LENGTH_END = 0xFFFFFFFFFFFFFFFF   # KNZ_LENGTH_END: a find window that runs to the end of the stream
+FIND_MAX_PATTERN = 256       # KNZ_FIND_MAX_PATTERN
 HEADER_SIZE_KEEP = -1        # KNZ_HEADER_SIZE_KEEP: the source's size field, moved by the growth (splice: the sum of the whole sources' fields)
 
 
@@ -149,6 +156,8 @@ def load_library(path=None):
     L.knz_dev_decompress_many_range.argtypes = [vp, C.POINTER(_Stream), C.POINTER(_BlockRange), C.c_int, vp]
     L.knz_dev_read_many.argtypes = [vp, C.POINTER(_Source), C.c_int, C.POINTER(_Read), C.c_int, vp]
     L.knz_dev_read.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, vp, u64p, vp]
+    L.knz_dev_find_many.argtypes = [vp, C.POINTER(_Source), C.c_int, C.POINTER(_Find), C.c_int, vp]
+    L.knz_dev_find.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, vp, C.c_uint64, u64p, vp]
     L.knz_dev_write_many.argtypes = [vp, vp, C.c_uint64, C.POINTER(_Write), C.c_int, C.c_int64, vp, C.c_uint64, u64p, vp]
     L.knz_dev_append.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.c_int64, vp, C.c_uint64, u64p, vp]
     L.knz_dev_splice_many.argtypes = [vp, C.POINTER(_SplicePart), C.c_int, C.POINTER(_SpliceOut), C.c_int, vp]
@@ -290,13 +299,11 @@ class Codec:
         self._chk(self.L.knz_dev_read(self.h, d_src, n_bytes, offset, length, d_dst, C.byref(out), stream))
         return out.value
 
-    def dev_read_many(self, sources, reads, check=False, stream=0):
-        """sources: [(d_src, n_bytes[, index_rows])], index_rows the [(bit, bits)] of dev_stream_index (or its first rows) as hints; reads: [(source, offset,
-        length, d_dst)]. Every distinct (source, block) the reads touch is decoded once, in one device batch (knz_dev_read_many). Returns
-        [(out_bytes, status)] per read; the call's own return value is in last_many_rc, the sources' statuses in last_source_status. Raises only with
-        check=True (the first failing read's code)."""
-        ns, nr = len(sources), len(reads)
-        src, rd, keep = (_Source * max(ns, 1))(), (_Read * max(nr, 1))(), []
+    @staticmethod
+    def _sources(sources):
+        """[(d_src, n_bytes[, index_rows])] -> the knz_source array of a read or find call, and what has to stay alive while it runs"""
+        ns = len(sources)
+        src, keep = (_Source * max(ns, 1))(), []
         for i, it in enumerate(sources):
             src[i].d_src, src[i].n = it[0], it[1]
             rows = it[2] if len(it) > 2 and it[2] else None
@@ -306,6 +313,16 @@ class Codec:
                     pos[j].bit, pos[j].bits = bit, bits
                 keep.append(pos)
                 src[i].pos, src[i].n_pos = pos, len(rows)
+        return src, keep
+
+    def dev_read_many(self, sources, reads, check=False, stream=0):
+        """sources: [(d_src, n_bytes[, index_rows])], index_rows the [(bit, bits)] of dev_stream_index (or its first rows) as hints; reads: [(source, offset,
+        length, d_dst)]. Every distinct (source, block) the reads touch is decoded once, in one device batch (knz_dev_read_many). Returns
+        [(out_bytes, status)] per read; the call's own return value is in last_many_rc, the sources' statuses in last_source_status. Raises only with
+        check=True (the first failing read's code)."""
+        ns, nr = len(sources), len(reads)
+        rd = (_Read * max(nr, 1))()
+        src, keep = self._sources(sources)
         for i, (s, offset, length, d_dst) in enumerate(reads):
             rd[i].source, rd[i].offset, rd[i].length, rd[i].d_dst = s, offset, length, d_dst
         rc = self.L.knz_dev_read_many(self.h, src, ns, rd, nr, stream)
@@ -314,6 +331,35 @@ class Codec:
         if check:
             self._chk(rc)
         return [(int(rd[i].out_bytes), int(rd[i].status)) for i in range(nr)]
+
+    def dev_find(self, d_src, n_bytes, pattern, d_hits=None, hits_cap=0, stream=0):
+        """Where `pattern` (bytes, 1 .. FIND_MAX_PATTERN of them) starts in the decoded stream at d_src (knz_dev_find): returns the number of matches,
+        overlapping ones included; the first min(that, hits_cap) decoded offsets go to the uint64 array d_hits on the device, in ascending order."""
+        pat = bytes(pattern)
+        out = C.c_uint64()
+        self._chk(self.L.knz_dev_find(self.h, d_src, n_bytes, C.c_char_p(pat) if pat else None, len(pat), d_hits, hits_cap, C.byref(out), stream))
+        return out.value
+
+    def dev_find_many(self, sources, finds, check=False, stream=0):
+        """sources: as dev_read_many's; finds: [(source, pattern, offset, length, d_hits, hits_cap)], matches of `pattern` that START in [offset, offset + length)
+        of the decoded stream (length None: to the end), d_hits a uint64 device array of hits_cap words (None / 0: count only). Every distinct
+        (source, block) the queries touch is decoded once, in one device batch, and searched in the workspace (knz_dev_find_many). Returns
+        [(n_hits, scanned, status)] per query; the call's own return value is in last_many_rc, the sources' statuses in last_source_status. Raises
+        only with check=True (the first failing query's code)."""
+        ns, nf = len(sources), len(finds)
+        fd = (_Find * max(nf, 1))()
+        src, keep = self._sources(sources)
+        for i, (s, pattern, offset, length, d_hits, hits_cap) in enumerate(finds):
+            buf = None if pattern is None else C.create_string_buffer(bytes(pattern), max(len(pattern), 1))
+            keep.append(buf)
+            fd[i].source, fd[i].pattern_len, fd[i].pattern = s, 0 if pattern is None else len(pattern), None if buf is None else C.addressof(buf)
+            fd[i].offset, fd[i].length, fd[i].d_hits, fd[i].hits_cap = offset, LENGTH_END if length is None else length, d_hits, hits_cap
+        rc = self.L.knz_dev_find_many(self.h, src, ns, fd, nf, stream)
+        self.last_many_rc = rc
+        self.last_source_status = [int(src[i].status) for i in range(ns)]
+        if check:
+            self._chk(rc)
+        return [(int(fd[i].n_hits), int(fd[i].scanned), int(fd[i].status)) for i in range(nf)]
 
     def dev_write_many(self, d_src, n_bytes, writes, d_dst, dst_cap, header_input_size=HEADER_SIZE_KEEP, check=False, stream=0):
         """writes: [(offset, length, d_data)], bytes of the decoded stream at d_src (offset may be OFFSET_END), applied in order; the new stream goes to

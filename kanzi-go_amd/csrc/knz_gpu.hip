@@ -27,6 +27,7 @@
 #include "layout.hip"
 #include "many.hip"
 #include "read.hip"
+#include "find.hip"
 #include "write.hip"
 #include "splice.hip"
 #include <algorithm>
@@ -360,5 +361,6 @@ extern "C" int knz_dev_compress_blocks(void* handle, const void* d_src, uint64_t
 #include "knz_multi.inc"
 #include "knz_many.inc"
 #include "knz_read.inc"
+#include "knz_find.inc"
 #include "knz_write.inc"
 #include "knz_splice.inc"

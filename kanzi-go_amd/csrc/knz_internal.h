@@ -113,6 +113,7 @@ struct Handle {
     PinnedBuf many_pinned;            // ... the table of streams (and the heads, or the ranges) on the host
     DevBuf read_tab, read_base;       // byte reads (read.hip): the table of reads with its entries behind it, the scan of the destination chunks
     PinnedBuf read_pinned;            // ... the table on the host: it goes up and comes back as one copy each
+    DevBuf find_cnt, find_bits;       // pattern search (find.hip, its table in read_tab / read_pinned): the tiles' hit counts and their scan, the tiles' match bitmaps
     DevBuf splice_tab;                // block splice (splice.hip): output rows, part rows, sources, boundaries, marks, pieces, the scan of the groups
     PinnedBuf splice_pinned;          // ... what the host fills of it: up in one copy, the output and part rows back in one
     void* pinned = nullptr;           // small pinned host area for results

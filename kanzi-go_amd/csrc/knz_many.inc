@@ -90,14 +90,17 @@ extern "C" int knz_dev_compress_many(void* handle, knz_stream* streams, int n, v
 // the selected frames are staged (knz_many_stage_range_kernel), so that walk, staging and batch follow the ranges and not the streams.
 // entered: the blocks of these entries that went into a decode batch (the first pass: a later one runs fewer of the same).
 // What happens to the decoded blocks, at ostride * b in the staging buffer, is the tail's choice: rd == nullptr places them into the entries' destinations ;
-// else they are gathered into the reads of knz_dev_read_many (knz_read.inc), and the entries' d_dst / dst_cap are not looked at.
+// rd: they are gathered into the reads of knz_dev_read_many (knz_read.inc) ; fd: they are searched for the patterns of knz_dev_find_many (knz_find.inc) ; the
+// entries' d_dst / dst_cap are then not looked at.
 struct ReadGather;
+struct FindScan;
 struct ManyBatchView {               // what the gather tail sees of the last pass: its entries' rows (host copy) and where the blocks were decoded
     const int* active; int A; const ManyStream* tab; const int32_t* status; uint64_t nblocks, ostride;
 };
 static int read_gather_tail(Handle* h, ReadGather& rd, const ManyBatchView& v, const knz_cfg& sc, int n, hipStream_t st);
+static int find_tail(Handle* h, FindScan& fd, const ManyBatchView& v, const knz_cfg& sc, int n, hipStream_t st);
 static int decompress_many_once(Handle* h, knz_stream* s, const uint32_t* firstBit, const knz_block_range* rg, const knz_cfg& sc, int n, hipStream_t st, uint64_t& entered,
-                                ReadGather* rd = nullptr) {
+                                ReadGather* rd = nullptr, FindScan* fd = nullptr) {
     uint64_t first_pass = 0;
     std::vector<int> active;
     std::vector<int32_t> status(n, 0);
@@ -190,9 +193,9 @@ static int decompress_many_once(Handle* h, knz_stream* s, const uint32_t* firstB
             active.swap(next);
             continue;
         }
-        if (rd) {
+        if (rd || fd) {
             const ManyBatchView v = {active.data(), A, tab, status.data(), nblocks, ostride};
-            const int grc = read_gather_tail(h, *rd, v, sc, n, st);
+            const int grc = rd ? read_gather_tail(h, *rd, v, sc, n, st) : find_tail(h, *fd, v, sc, n, st);
             if (grc) return grc;
             break;
         }

@@ -64,6 +64,27 @@ __device__ __forceinline__ void knz_read_finish(ReadRow& r, uint64_t& chunks, in
     chunks = out ? ((r.dst + out + 15) >> 4) - (r.dst >> 4) : 0;
 }
 
+// fail / stop / stop_len of the window of entries [first, first + count), taken by one whole wave (every lane calls it and gets the same answer):
+// what the long reads' plan and the find calls' plan (find.hip) share
+__device__ __forceinline__ void knz_read_window_wave(const ReadArgs& a, uint32_t first, uint32_t count, uint32_t lane, int32_t& fail, uint32_t& stop, uint32_t& stop_len) {
+    uint32_t bad = count;                                                 // the lane's first failing / first short entry
+    stop = count;
+    for (uint32_t j = lane; j < count; j += 64) {
+        uint32_t len;
+        const int32_t st = knz_read_entry(a, first + j, len);
+        if (st != 0 && bad == count) bad = j;
+        if (st == 0 && len < a.block_size && stop == count) stop = j;
+    }
+    for (int d = 32; d >= 1; d >>= 1) {
+        const uint32_t b2 = wave_shfl(bad, (int)(lane ^ d)), s2 = wave_shfl(stop, (int)(lane ^ d));
+        bad = min(bad, b2); stop = min(stop, s2);
+    }
+    fail = 0; stop_len = 0;
+    uint32_t len;
+    if (bad < count) fail = knz_read_entry(a, first + bad, len);
+    else if (stop < count) { knz_read_entry(a, first + stop, len); stop_len = len; }
+}
+
 // wide == 0: one thread per read, reads over more than KNZ_READ_LONG entries left out ; wide == 1: one wave per read of long_ids
 __global__ __launch_bounds__(256) void knz_read_plan_kernel(ReadArgs a, uint32_t wide) {
     const uint32_t t = blockIdx.x * 256 + threadIdx.x;
@@ -87,22 +108,10 @@ __global__ __launch_bounds__(256) void knz_read_plan_kernel(ReadArgs a, uint32_t
     const uint32_t id = a.long_ids[t >> 6];
     ReadRow& r = a.reads[id];
     if (r.status != 0) { if (lane == 0) { r.out = 0; a.base[id] = 0; } return; }
-    uint32_t bad = r.count, stop = r.count;                               // the lane's first failing / first short entry
-    for (uint32_t j = lane; j < r.count; j += 64) {
-        uint32_t len;
-        const int32_t st = knz_read_entry(a, r.first + j, len);
-        if (st != 0 && bad == r.count) bad = j;
-        if (st == 0 && len < a.block_size && stop == r.count) stop = j;
-    }
-    for (int d = 32; d >= 1; d >>= 1) {
-        const uint32_t b2 = wave_shfl(bad, (int)(lane ^ d)), s2 = wave_shfl(stop, (int)(lane ^ d));
-        bad = min(bad, b2); stop = min(stop, s2);
-    }
+    int32_t fail;
+    uint32_t stop, stop_len;
+    knz_read_window_wave(a, r.first, r.count, lane, fail, stop, stop_len);
     if (lane != 0) return;
-    int32_t fail = 0;
-    uint32_t stop_len = 0, len;
-    if (bad < r.count) fail = knz_read_entry(a, r.first + bad, len);
-    else if (stop < r.count) { knz_read_entry(a, r.first + stop, len); stop_len = len; }
     knz_read_finish(r, a.base[id], fail, stop, stop_len, a.block_size);
 }
 
