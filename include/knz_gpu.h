@@ -349,6 +349,48 @@ int knz_dev_append(void* handle, const void* d_src, uint64_t n_bytes, const void
                    int64_t header_input_size, void* d_dst, uint64_t dst_cap, uint64_t* out_bytes, void* hip_stream);
 
 /*
+ * Byte writes into MANY streams: T targets (one source stream, one new stream each) and W writes that name their target, in one call. For every target
+ * the call delivers what knz_dev_write_many delivers for that target alone (its text above is the specification): the writes of target t are the rows
+ * with target == t, in index order (rows of different targets may interleave), and d_dst[0 .. out_bytes), out_bytes, the target's status (the single
+ * call's return value) and its writes' statuses are the single call's. The work of all targets goes through ONE framing pass, ONE decode batch, ONE
+ * overlay, ONE encode batch and ONE splice: launches and host synchronisations do not grow with T, and the chains of the transforms run side by side.
+ *   failure:    per target, all or nothing: a failed target has out_bytes 0 and NO byte of its d_dst is written, every other target completes. A damaged
+ *               touched block, a hole, a header that does not parse, another configuration than the handle's, a dst_cap too small fail their target
+ *               only. The call returns 0 or the status of the first failed target (lowest index).
+ *   no writes:  a target that no write names gets status 0 and out_bytes 0, nothing of it is read or written (the single call's n_writes <= 0).
+ *   arguments:  n_targets <= 0 returns 0. NULL targets, or NULL writes with n_writes > 0: KNZ_ERR_MISSING_PARAM. A write whose target >= n_targets makes
+ *               the call malformed: KNZ_ERR_INVALID_PARAM for the call, on every target and every write, nothing is written (the splice call's rule
+ *               for `out`). NULL d_src or d_dst (KNZ_ERR_MISSING_PARAM ; the target's writes are not looked at and keep status 0), a write's own
+ *               arguments, d_src or d_dst off 4 bytes: the single call's codes, on that target. d_dst on another device than the call's lane, or
+ *               d_dst[0 .. dst_cap) overlapping a source of the call or another target's range (checked on the host from the pointers, over the
+ *               targets some write names): KNZ_ERR_INVALID_PARAM on that target and on its writes. The same d_src may serve several targets: each
+ *               gets its own decoded copies of the blocks it touches, and the source is walked once.
+ *   lanes:      on a handle of several lanes the call runs on the lane that owns targets[0].d_dst.
+ *   workspace:  a batch whose workspace the device refuses is taken in halves of the target list (the many calls' rule). A target's own touched blocks
+ *               and block streams have to fit: a target that does not fit alone takes the workspace's code on itself and on its writes, the others
+ *               complete.
+ *   counters:   KNZ_COUNTER_DECODE_BATCH_BLOCKS: the touched existing blocks, summed over the targets that reached the decode batch ;
+ *               KNZ_COUNTER_ENCODE_BATCH_BLOCKS: the rows of the encode batch, touched and new blocks of all targets.
+ *   safety:     whatever a stream says, every read stays inside its own d_src[0 .. n_bytes) rounded up to 4 and every write inside its own target's
+ *               dst_cap. Outputs may follow each other to the word: nothing outside a stream's own 32-bit words is written. Nothing is atomic: the same
+ *               input gives the same bytes.
+ */
+typedef struct {
+    const void* d_src; uint64_t n_bytes;   /* the source stream: device, 4-byte aligned, readable to the next multiple of 4 */
+    void* d_dst; uint64_t dst_cap;         /* the new stream: 4-byte aligned; the single calls' rule for dst_cap */
+    int64_t header_input_size;             /* as knz_dev_write_many; KNZ_HEADER_SIZE_KEEP allowed */
+    uint64_t out_bytes;                    /* result */
+    int32_t status, reserved;              /* result */
+} knz_write_target;
+typedef struct {
+    uint32_t target, reserved0;            /* index into targets[] */
+    uint64_t offset, length;               /* as knz_write; offset may be KNZ_OFFSET_END */
+    const void* d_data;                    /* device, ANY alignment, `length` bytes readable */
+    int32_t status, reserved;              /* result */
+} knz_write_to;
+int knz_dev_write_streams(void* handle, knz_write_target* targets, int n_targets, knz_write_to* writes, int n_writes, void* hip_stream);
+
+/*
  * Block splice: parts (source stream, block range) become output streams, and nothing but whole frames moves. Blocks are independent, a frame carries no
  * block id, the checksum travels inside the frame and the header does not depend on the block count: concatenating K streams, slicing blocks [from, to)
  * out of one, splitting one into K or regrouping any list of parts into any number of outputs needs no decode chain and no encode chain.

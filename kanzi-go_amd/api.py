@@ -88,6 +88,16 @@ class _Write(C.Structure):
     _fields_ = [("offset", C.c_uint64), ("length", C.c_uint64), ("d_data", C.c_void_p), ("status", C.c_int32), ("reserved", C.c_int32)]
 
 
+class _WriteTarget(C.Structure):
+    _fields_ = [("d_src", C.c_void_p), ("n_bytes", C.c_uint64), ("d_dst", C.c_void_p), ("dst_cap", C.c_uint64), ("header_input_size", C.c_int64),
+                ("out_bytes", C.c_uint64), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
+class _WriteTo(C.Structure):
+    _fields_ = [("target", C.c_uint32), ("reserved0", C.c_uint32), ("offset", C.c_uint64), ("length", C.c_uint64), ("d_data", C.c_void_p),
+                ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
 class _SplicePart(C.Structure):
     _fields_ = [("d_src", C.c_void_p), ("n_bytes", C.c_uint64), ("from_block", C.c_uint32), ("to_block", C.c_uint32), ("out", C.c_uint32),
                 ("status", C.c_int32), ("blocks", C.c_uint64), ("bits", C.c_uint64)]
@@ -160,6 +170,7 @@ def load_library(path=None):
     L.knz_dev_find.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, vp, C.c_uint64, u64p, vp]
     L.knz_dev_write_many.argtypes = [vp, vp, C.c_uint64, C.POINTER(_Write), C.c_int, C.c_int64, vp, C.c_uint64, u64p, vp]
     L.knz_dev_append.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.c_int64, vp, C.c_uint64, u64p, vp]
+    L.knz_dev_write_streams.argtypes = [vp, C.POINTER(_WriteTarget), C.c_int, C.POINTER(_WriteTo), C.c_int, vp]
     L.knz_dev_splice_many.argtypes = [vp, C.POINTER(_SplicePart), C.c_int, C.POINTER(_SpliceOut), C.c_int, vp]
     L.knz_dev_concat.argtypes = [vp, C.POINTER(vp), u64p, C.c_int, C.c_int64, vp, C.c_uint64, u64p, vp]
     L.knz_dev_slice.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int64, vp, C.c_uint64, u64p, vp]
@@ -386,6 +397,25 @@ class Codec:
         if check:
             self._chk(rc)
         return out.value
+
+    def dev_write_streams(self, targets, writes, check=False, stream=0):
+        """targets: [(d_src, n_bytes, d_dst, dst_cap[, header_input_size])], one source stream and one new stream each (header size default
+        HEADER_SIZE_KEEP); writes: [(target, offset, length, d_data)], each into the decoded stream of its target, applied per target in index order
+        (knz_dev_write_streams). Every target gets what dev_write_many gives for it alone, all of them through one decode batch, one encode batch and
+        one splice. Returns ([(out_bytes, status)] per target, [status] per write); the call's own return value is in last_many_rc. A failed target has
+        out_bytes 0 and its d_dst untouched, the others complete. Raises only with check=True."""
+        n, m = len(targets), len(writes)
+        ta, wa = (_WriteTarget * max(n, 1))(), (_WriteTo * max(m, 1))()
+        for i, it in enumerate(targets):
+            ta[i].d_src, ta[i].n_bytes, ta[i].d_dst, ta[i].dst_cap = it[0], it[1], it[2], it[3]
+            ta[i].header_input_size = it[4] if len(it) > 4 and it[4] is not None else HEADER_SIZE_KEEP
+        for i, (target, offset, length, d_data) in enumerate(writes):
+            wa[i].target, wa[i].offset, wa[i].length, wa[i].d_data = target, offset, length, d_data
+        rc = self.L.knz_dev_write_streams(self.h, ta, n, wa, m, stream)
+        self.last_many_rc = rc
+        if check:
+            self._chk(rc)
+        return [(int(ta[i].out_bytes), int(ta[i].status)) for i in range(n)], [int(wa[i].status) for i in range(m)]
 
     def dev_splice_many(self, parts, outs, check=False, stream=0):
         """parts: [(d_src, n_bytes, from_block, to_block, out)], blocks from_block .. to_block - 1 (ids from 1; to_block None: through the last) of the stream at

@@ -29,6 +29,7 @@
 #include "read.hip"
 #include "find.hip"
 #include "write.hip"
+#include "write_streams.hip"
 #include "splice.hip"
 #include <algorithm>
 #include <cstdio>
@@ -363,4 +364,5 @@ extern "C" int knz_dev_compress_blocks(void* handle, const void* d_src, uint64_t
 #include "knz_read.inc"
 #include "knz_find.inc"
 #include "knz_write.inc"
+#include "knz_write_streams.inc"
 #include "knz_splice.inc"
