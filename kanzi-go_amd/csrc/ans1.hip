@@ -439,7 +439,8 @@ __device__ __forceinline__ void knz_a1e_run_group(uint32_t& st, const uint4* e, 
     knz_a1e_run4(st, e[12], e[13], e[14], e[15], mine + R * 64 + 12);
 }
 
-__global__ __launch_bounds__(64) void knz_ans1_encode_asm_kernel(Ans1Args a, const uint4* ent) {
+// (the one-wave form: KNZ_ANS1_ENC_ONE_WAVE, A/B and cross-check of the two-wave kernel below)
+__global__ __launch_bounds__(64) void knz_ans1_encode_asm1_kernel(Ans1Args a, const uint4* ent) {
     __shared__ __attribute__((aligned(16))) uint32_t s_w[3 * KNZ_ANS1_GROUP * 4];   // state in front of the renormalisation of (group, state, step) of the current 48 steps
     const int lane = threadIdx.x;
     const uint32_t slotId = blockIdx.x;
@@ -515,6 +516,178 @@ __global__ __launch_bounds__(64) void knz_ans1_encode_asm_kernel(Ans1Args a, con
     }
 }
 #endif
+
+// The coder as a workgroup of two waves. Of the one-wave kernel's 440 instructions a turn (48 steps) about 85 place the renormalisation words: they
+// re-read the 192 candidate states, take three ballots against xMax, count, and make three predicated pairs of byte stores. None of that is on the
+// state's dependence chain, and the states leave through LDS anyway: so wave 0 codes (entries in, knz_a1e_run_group, states out into a ring of
+// KNZ_A1E_RING turns) and wave 1 places (reads a turn's states, loads the xMax of its (step, state) itself, ballots, counts, stores the words
+// descending from payEnd). They meet through LDS words: sync[0] = turns coded, sync[1] = turns placed, sync[2] = the coder is done and its four
+// final states stand in fin[], sync[3] = one side gave up. A wave's LDS operations complete in order, so a count stored behind a turn's states (or
+// behind the reads of them) says that they are there (or have been taken); wave_sync_lds() keeps the compiler from moving them across. The coder
+// reads the placer's count once a turn, one turn ahead of the use (the slot it is about to overwrite must have been taken: with eight turns of
+// ring it never waits in practice); every wait pauses, watches the give-up word and is bounded, so the kernel returns whatever happens to the
+// other wave: the block then carries KNZ_ERR_PROCESS_BLOCK. (That turns a stall which is no fault of the data, a wave held for seconds by a debugger
+// or by preemption, into a failed compress, where the Huffman walker falls back to its serial parser. Both waves are resident in one workgroup
+// and a wait is some seconds long, so this is a backstop against a hang, not a path: the caller compresses again, or with KNZ_ANS1_ENC_ONE_WAVE.) The emulator build runs the same structure with the C++ step of knz_ans1_encode_kernel.
+#define KNZ_A1E_RING 8                                  // turns of 48 steps in the ring (6 KiB of LDS)
+#define KNZ_A1E_TURN (3 * KNZ_ANS1_GROUP)
+#define KNZ_A1E_SPINS (1u << 24)                       // polls of a wait before it gives up (a poll is >= ~100 ns: seconds)
+// the words the two waves meet through (relaxed workgroup-scope accesses: plain ds_read / ds_write, never merged, hoisted or dropped)
+#ifndef KNZ_HIP_EMU
+__device__ __forceinline__ uint32_t knz_lds_poll(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+__device__ __forceinline__ void knz_lds_post(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+#else
+inline uint32_t knz_lds_poll(const uint32_t* p) { return *(const volatile uint32_t*)p; }
+inline void knz_lds_post(uint32_t* p, uint32_t v) { *(volatile uint32_t*)p = v; }
+#endif
+struct __attribute__((aligned(16))) KnzA1eShared {
+    uint32_t ring[KNZ_A1E_RING][KNZ_A1E_TURN * 4];     // state in front of the renormalisation of (turn, group, state, step)
+    uint32_t fin[4];
+    uint32_t sync[4];
+};
+
+#ifdef KNZ_HIP_EMU
+// the C++ step, the states to the slots the hand-written step uses
+template <int R>
+__device__ __forceinline__ void knz_a1e_run_group(uint32_t& st, const uint4* e, uint32_t* mine) {
+#pragma unroll
+    for (int j = 0; j < KNZ_ANS1_GROUP; j++) {
+        mine[R * 64 + j] = st;
+        st = st >= e[j].y ? (st >> 16) : st;
+        const uint32_t qq = (uint32_t)(((uint64_t)st * e[j].x) >> 32) >> (e[j].w & 31u);
+        st = st + e[j].z + knz_mul24(qq, e[j].w >> 16);
+    }
+}
+#endif
+
+__global__ __launch_bounds__(128) void knz_ans1_encode_asm_kernel(Ans1Args a, const uint4* ent) {
+    __shared__ KnzA1eShared sh;
+    const int lane = threadIdx.x & 63;
+    const uint32_t slotId = blockIdx.x;
+    uint32_t b, n; const uint8_t* src; bool bad;
+    const uint32_t steps = knz_ans1_steps(a, slotId, b, n, src, bad);
+    const bool live = n != 0;
+    const uint32_t nturns = steps ? (steps + 2 * KNZ_ANS1_GROUP + KNZ_A1E_TURN - 1) / KNZ_A1E_TURN : 0u;     // turns t0 = 0, 48, .. < steps + 32
+    const uint4* __restrict__ base = ent + (size_t)slotId * KNZ_ANS1_ENT_STRIDE;
+    if (threadIdx.x < 4) sh.sync[threadIdx.x] = 0;
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        // ---- the coding wave ------------------------------------------------------------------------------------------------------------
+        const uint4* __restrict__ my = base + (size_t)(lane & 3);           // lanes 4..63 mirror lanes 0..3 (same entries, same state, same LDS words)
+        uint32_t st = 1u << 15;
+        uint4 buf0[KNZ_ANS1_GROUP], buf1[KNZ_ANS1_GROUP], buf2[KNZ_ANS1_GROUP];
+        auto load_group = [&](const uint4* g, uint4* e) {
+#pragma unroll
+            for (int j = 0; j < KNZ_ANS1_GROUP; j++) e[j] = g[j * 4];
+        };
+#pragma unroll
+        for (int j = 0; j < KNZ_ANS1_GROUP; j++) { buf0[j].x = 0; buf0[j].y = 0xFFFFFFFFu; buf0[j].z = 0; buf0[j].w = 0; buf1[j] = buf0[j]; }
+        uint32_t placed = 0;                                                // the placer's count as last read (it only grows: an old value errs on the safe side)
+        uint32_t slot = 0;
+        bool gaveUp = false;
+        for (uint32_t turn = 0; turn < nturns; turn++) {
+            if (turn >= placed + KNZ_A1E_RING) {                            // the slot still holds a turn that has not been placed
+                uint32_t spins = 0;
+                while (turn >= (placed = knz_lds_poll(&sh.sync[1])) + KNZ_A1E_RING) {
+                    if (knz_lds_poll(&sh.sync[3]) != 0 || ++spins > KNZ_A1E_SPINS) { gaveUp = true; break; }
+                    wave_spin_pause();
+                }
+                if (gaveUp) break;
+            }
+            const uint32_t seen = knz_lds_poll(&sh.sync[1]);                // for the next turn: the read is under way while this one is coded
+            uint32_t* mine = sh.ring[slot] + 16 * (lane & 3);               // this lane's state: 16 steps of a group side by side
+            load_group(my, buf2); knz_a1e_run_group<0>(st, buf0, mine);
+            load_group(my + 4 * KNZ_ANS1_GROUP, buf0); knz_a1e_run_group<1>(st, buf1, mine);
+            load_group(my + 8 * KNZ_ANS1_GROUP, buf1); knz_a1e_run_group<2>(st, buf2, mine);
+            my += 4 * KNZ_A1E_TURN;
+            wave_sync_lds();
+            knz_lds_post(&sh.sync[0], turn + 1);                            // (every lane stores the same word: no lane is singled out on the chain)
+            placed = seen;
+            slot = slot + 1 == KNZ_A1E_RING ? 0 : slot + 1;
+        }
+        if (lane < 4) sh.fin[lane] = st;
+        wave_sync_lds();
+        if (gaveUp) knz_lds_post(&sh.sync[3], 1u);
+        knz_lds_post(&sh.sync[2], 1u);
+        return;
+    }
+    // ---- the placer -----------------------------------------------------------------------------------------------------------------------
+    uint8_t* slotMem = a.scratch + (size_t)slotId * KNZ_ANS1_SLOT;
+    uint8_t* payEnd = slotMem + KNZ_ANS1_PAY_OFF + KNZ_ANS1_PAY_CAP;
+    uint32_t flushed = 0;
+    bool gaveUp = false;
+    const uint64_t below = ((uint64_t)1 << lane) - 1;
+    const uint32_t fi = 16u * (uint32_t)(lane & 3) + (uint32_t)(lane >> 2);     // lane = 4 * step + state reads slot [state][step]
+    // xMax of (step = lane >> 2, state = lane & 3) of group g (0..2) of a turn: the turn at t0 codes the steps t0 - 32 .. t0 + 15 (the coder's first two
+    // buffers start neutral); loaded two turns ahead
+    auto xmax = [&](uint32_t turn, uint32_t g) -> uint32_t {
+        const uint32_t t = turn * KNZ_A1E_TURN + g * KNZ_ANS1_GROUP;
+        return (turn < nturns && t >= 2 * KNZ_ANS1_GROUP) ? base[(size_t)(t - 2 * KNZ_ANS1_GROUP) * 4 + (uint32_t)lane].y : 0xFFFFFFFFu;
+    };
+    uint32_t xa[3], xb[3], xc[3];
+#pragma unroll
+    for (uint32_t g = 0; g < 3; g++) { xa[g] = xmax(0, g); xb[g] = xmax(1, g); xc[g] = xmax(2, g); }
+    uint32_t slot = 0;
+    for (uint32_t turn = 0; turn < nturns; turn++) {
+        uint32_t spins = 0;
+        while (knz_lds_poll(&sh.sync[0]) <= turn) {
+            if (knz_lds_poll(&sh.sync[3]) != 0 || ++spins > KNZ_A1E_SPINS) { gaveUp = true; break; }
+            wave_spin_pause();
+        }
+        if (gaveUp) break;
+        wave_sync_lds();
+        const uint32_t* w = sh.ring[slot];
+        const uint32_t v0 = knz_lds_poll(w + fi), v1 = knz_lds_poll(w + 64 + fi), v2 = knz_lds_poll(w + 128 + fi);
+        const uint64_t m0 = wave_ballot(v0 >= xa[0]), m1 = wave_ballot(v1 >= xa[1]), m2 = wave_ballot(v2 >= xa[2]);
+        wave_sync_lds();
+        knz_lds_post(&sh.sync[1], turn + 1);                                // the states are in registers: the slot is free
+        const uint32_t c0 = (uint32_t)__popcll(m0), c1 = (uint32_t)__popcll(m1), c2 = (uint32_t)__popcll(m2);
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+            const uint64_t m = r == 0 ? m0 : (r == 1 ? m1 : m2);
+            const uint32_t before = r == 0 ? 0u : (r == 1 ? c0 : c0 + c1);
+            if ((m >> lane) & 1) {
+                const uint32_t pos = flushed + before + (uint32_t)__popcll(m & below);
+                const uint32_t wv = r == 0 ? v0 : (r == 1 ? v1 : v2);
+                uint8_t* p = payEnd - 2 * ((size_t)pos + 1);
+                p[0] = (uint8_t)(wv >> 8);
+                p[1] = (uint8_t)wv;
+            }
+        }
+        flushed += c0 + c1 + c2;
+#pragma unroll
+        for (uint32_t g = 0; g < 3; g++) { xa[g] = xb[g]; xb[g] = xc[g]; xc[g] = xmax(turn + 3, g); }
+        slot = slot + 1 == KNZ_A1E_RING ? 0 : slot + 1;
+    }
+    if (gaveUp) knz_lds_post(&sh.sync[3], 1u);
+    for (uint32_t spins = 0; !gaveUp && knz_lds_poll(&sh.sync[2]) == 0;) {  // the final states
+        if (++spins > KNZ_A1E_SPINS) { gaveUp = true; knz_lds_post(&sh.sync[3], 1u); break; }
+        wave_spin_pause();
+    }
+    wave_sync_lds();
+    if (knz_lds_poll(&sh.sync[3]) != 0) gaveUp = true;
+    if ((bad || (gaveUp && live)) && lane == 0) a.blk_status[b] = KNZ_ERR_PROCESS_BLOCK;
+    if (live && !gaveUp && lane == 0) {
+        const uint32_t st = knz_lds_poll(&sh.fin[0]), s1 = knz_lds_poll(&sh.fin[1]), s2 = knz_lds_poll(&sh.fin[2]), s3 = knz_lds_poll(&sh.fin[3]);
+        const uint32_t end4 = n & ~3u;
+        const uint32_t tail = n & 3;
+        for (uint32_t i = 0; i < tail; i++) payEnd[i] = src[end4 + i];
+        const uint32_t nbytes = 2 * flushed + tail;
+        uint32_t w[8];
+        for (int i = 0; i < 8; i++) w[i] = 0;
+        KnzBitWriter bw;
+        bw.init(w);
+        knz_put_varint(bw, nbytes);
+        bw.put(st, 32); bw.put(s1, 32); bw.put(s2, 32); bw.put(s3, 32);
+        uint32_t* u1 = (uint32_t*)(slotMem + KNZ_ANS1_U1_OFF);
+        for (int i = 0; i < 8; i++) u1[i] = knz_bswap32(w[i]);
+        uint32_t* ubits = a.unit_bits + (size_t)slotId * KNZ_UNITS_PER_CHUNK;
+        uint32_t* usrc = a.unit_src + (size_t)slotId * KNZ_UNITS_PER_CHUNK;
+        ubits[1] = bw.pos;
+        ubits[2] = 8 * nbytes;
+        usrc[2] = (uint32_t)(KNZ_ANS1_PAY_OFF + KNZ_ANS1_PAY_CAP - 2 * flushed);
+    }
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Decoder

@@ -109,6 +109,120 @@ __device__ __forceinline__ uint32_t knz_read_varint(R& r) {
 template <typename R>
 __device__ static bool knz_ans1_parse_header(R& r, uint16_t* freq16, uint32_t& lrOut, int& totalAlpha, uint64_t* ctxpos, bool store);
 
+// Position walk of an order-1 rANS chunk header (decodeHeader, ANSRangeCodec.go:605-710, 256 contexts back to back) for the block walker:
+// what knz_ans1_parse_header(r, nullptr, ...) does through KnzWaveReader, written for this one job. A block of executable-like data has
+// ~32 frequency groups in every one of its 256 contexts, ~16 000 dependent reads per block in front of every decode, and a lone wave pays
+// ~2.4 ns for each instruction it issues: so a group is one fetch at a scalar bit position, the width check and the add.
+//   window   lane l holds stream words base+l (wa) and base+l+1 (wb), byte-swapped ONCE when they enter: the 64 bits at any word k < 64
+//            of the window are two v_readlane with the same lane select, no straddle case, no window to rebuild behind a long skip;
+//   position one scalar, rp = bits behind word `base` (the absolute position is base * 32 + rp, formed once per context);
+//   shift    the window moves on by 48 words when the position passes word 64 (a group: two words needed) or word 54 (an alphabet: its
+//            masks take up to ten words, counted by the lanes side by side); the next window is loaded when the current one is
+//            entered, a whole shift (~35 groups, a context of a long block) ahead of its use: the chain context k -> k + 1 does not
+//            wait for memory;
+//   ctxpos   lane k & 63 keeps the position of context k and the wave stores 64 of them at a time.
+// Words at or past nwords read as 0, as they do for the readers above. ALL 64 lanes must call it uniformly.
+#define KNZ_A1W_STEP 48u                                // words a shift moves the window on
+struct KnzAns1Walk {
+    const uint32_t* words;
+    uint64_t nwords;
+    uint64_t base;        // stream word held by lane 0 of wa
+    uint32_t rp;          // position in bits behind word `base`
+    uint32_t wa, wb;      // the window, byte-swapped
+    uint32_t na, nb;      // the window at base + 48 as loaded
+    int lane;
+    __device__ __forceinline__ void load(uint64_t wbase, uint32_t& x, uint32_t& y) const {
+        const uint64_t i = wbase + (uint64_t)lane;
+        if (wbase + 65 <= nwords) { x = words[i]; y = words[i + 1]; }      // wave-uniform: the whole window is inside
+        else { x = i < nwords ? words[i] : 0u; y = i + 1 < nwords ? words[i + 1] : 0u; }
+    }
+    __device__ __forceinline__ void init(const uint8_t* s, uint64_t nbytes, uint64_t bitpos) {
+        words = (const uint32_t*)s;
+        nwords = (nbytes + 3) >> 2;
+        lane = lane_id();
+        // (the caller's position is the same in every lane, which the compiler cannot see behind KnzWaveReader: said here, the walk stays on the scalar unit)
+        base = ((uint64_t)wave_uniform((uint32_t)(bitpos >> 37)) << 32) | wave_uniform((uint32_t)(bitpos >> 5));
+        rp = wave_uniform((uint32_t)bitpos & 31u);
+        uint32_t x, y;
+        load(base, x, y);
+        wa = knz_bswap32(x); wb = knz_bswap32(y);
+        load(base + KNZ_A1W_STEP, na, nb);
+    }
+    __device__ __forceinline__ void shift() {
+        wa = knz_bswap32(na); wb = knz_bswap32(nb);
+        base += KNZ_A1W_STEP;
+        rp -= 32u * KNZ_A1W_STEP;
+        load(base + KNZ_A1W_STEP, na, nb);
+    }
+    // the 64 bits at the position's word, left-aligned at the position: the top 33 bits at least are stream bits
+    __device__ __forceinline__ uint64_t fetch() const {
+        const uint32_t k = rp >> 5;
+        return (((uint64_t)wave_readlane(wa, k) << 32) | wave_readlane(wb, k)) << (rp & 31u);
+    }
+    __device__ __forceinline__ uint64_t tell() const { return (base << 5) + rp; }
+    // number of set bits among the next nbits (<= 256) bits: lane l counts what its word holds of them (the position is inside the first 54 words)
+    __device__ __forceinline__ uint32_t popcount_bits(uint32_t nbits) const {
+        const int s = (int)rp - 32 * lane, e = s + (int)nbits;
+        const uint32_t lo = (uint32_t)min(max(s, 0), 32), hi = (uint32_t)min(max(e, 0), 32);            // the word's bits [lo, hi), counted from its top
+        const uint32_t m = (uint32_t)(0xFFFFFFFF00000000ull >> hi) & (uint32_t)(0xFFFFFFFFull >> lo);
+        return wave_readlane(wave_scan_incl((uint32_t)__popc(wa & m)), 63);
+    }
+};
+
+// Returns false on an invalid header, as knz_ans1_parse_header does (the same conditions). On success `endpos` is the position behind the
+// last context. ctxpos (or null) takes the 257 positions: every lane stores the ones it keeps, lane 0 the last.
+__device__ static bool knz_ans1_walk_header(const uint8_t* stream, uint64_t nbytes, uint64_t pos, uint64_t* ctxpos, int& totalAlpha, uint64_t& endpos) {
+    KnzAns1Walk w;
+    w.init(stream, nbytes, pos);
+    const uint64_t origin = w.base << 5;                 // positions are kept as 32-bit distances from here (a header is < 2^21 bits)
+    uint32_t moved = 0;                                  // bits the window has moved on
+    const uint32_t lr = 8 + (uint32_t)(w.fetch() >> 61);
+    w.rp += 3;
+    totalAlpha = 0;
+    endpos = pos;
+    if (lr > 16) return false;
+    uint32_t llr = 3;
+    while ((1u << llr) <= lr) llr++;
+    uint32_t mine = 0;                                   // distance of context (64 * i + lane) from the origin
+    uint32_t total = 0;
+    bool ok = true;
+    int k = 0;
+    for (; k < 256 && ok; k++) {
+        if (__builtin_expect(w.rp >= 32u * 54u, 0)) do { w.shift(); moved += 32u * KNZ_A1W_STEP; } while (w.rp >= 32u * 54u);
+        if (w.lane == (k & 63)) mine = moved + w.rp;
+        const uint64_t h = w.fetch();
+        uint32_t count;
+        if ((h >> 63) == 0) { count = ((h >> 62) & 1) ? 0u : 256u; w.rp += 2; }
+        else {
+            const uint32_t nbits = 8u * (((uint32_t)(h >> 58) & 31u) + 1u);
+            w.rp += 6;
+            count = w.popcount_bits(nbits);
+            w.rp += nbits;
+        }
+        total += count;
+        if (count > 1) {
+            const uint32_t chk = count < 64 ? 6u : 8u;
+            uint32_t widest = 0;
+            uint32_t left = count - 1;
+            do {
+                if (__builtin_expect(w.rp >= 32u * 64u, 0)) do { w.shift(); moved += 32u * KNZ_A1W_STEP; } while (w.rp >= 32u * 64u);
+                const uint32_t logMax = (uint32_t)(w.fetch() >> (64 - llr));
+                const uint32_t n = min(chk, left);
+                widest = max(widest, logMax);
+                w.rp += llr + n * logMax;
+                left -= n;
+            } while (left != 0);
+            ok = widest <= lr;                           // (1 << logMax) > scale in any group: the header is invalid (the positions behind it are not used)
+        }
+        if (ctxpos && ((k & 63) == 63 || !ok)) { if (w.lane <= (k & 63)) ctxpos[(k & ~63) + w.lane] = origin + mine; }
+    }
+    totalAlpha = (int)total;
+    if (!ok) return false;
+    endpos = origin + moved + w.rp;
+    if (ctxpos && w.lane == 0) ctxpos[256] = endpos;
+    return true;
+}
+
 struct WalkStreamArgs {
     const uint8_t* stream; uint64_t nbytes;
     uint64_t first_bit;          // first block's framing
@@ -220,6 +334,7 @@ struct WalkBlocksArgs {
     uint64_t out_base, out_stride, out_cap;
     uint32_t stream_block_size;
     uint64_t* ans1_ctx_bit;       // [nblocks * CPB][257] rANS order 1: bit position of every context header of a chunk (+ the end), or null
+    uint32_t ans1_walk_plain;     // 1 (KNZ_ANS1_WALK_PLAIN): the chunk headers are walked by knz_ans1_parse_header through KnzWaveReader (A/B and cross-check)
 };
 
 // Skips one signed Exp-Golomb code (ExpGolombCodec.go:159-190): '1' or L zeros, 1, L+1 bits.

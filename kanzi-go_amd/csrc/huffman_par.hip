@@ -723,8 +723,16 @@ __device__ __forceinline__ void knz_walk_block_body(const WalkBlocksArgs& a, con
                 if ((int32_t)szb < 0 || (uint64_t)szb >= 2ull * preLen) status = KNZ_ERR_PROCESS_BLOCK;
                 r.seek(r.tell() + 56 + 8ull * szb);
             } else if (entropy == KNZ_E_ANS1) {
-                uint32_t lr; int total;
-                if (!knz_ans1_parse_header(r, nullptr, lr, total, a.ans1_ctx_bit ? a.ans1_ctx_bit + ((size_t)b * cpb + k) * 257 : nullptr, writer) || total == 0) { status = KNZ_ERR_PROCESS_BLOCK; break; }
+                int total;
+                uint64_t* ctxpos = a.ans1_ctx_bit ? a.ans1_ctx_bit + ((size_t)b * cpb + k) * 257 : nullptr;
+                if (a.ans1_walk_plain) {
+                    uint32_t lr;
+                    if (!knz_ans1_parse_header(r, nullptr, lr, total, ctxpos, writer) || total == 0) { status = KNZ_ERR_PROCESS_BLOCK; break; }
+                } else {                                               // the walk written for this job (huffman_dec.hip); r takes over behind the last context
+                    uint64_t hdrEnd;
+                    if (!knz_ans1_walk_header(a.stream, a.nbytes, r.tell(), ctxpos, total, hdrEnd) || total == 0) { status = KNZ_ERR_PROCESS_BLOCK; break; }
+                    r.seek(hdrEnd);
+                }
                 const uint32_t szb = knz_read_varint(r);
                 if (szb >= (1u << 27)) status = KNZ_ERR_PROCESS_BLOCK;
                 r.seek(r.tell() + 128 + 8ull * szb);

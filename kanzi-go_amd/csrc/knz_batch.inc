@@ -129,6 +129,7 @@ static int ans1_encode_stage(Handle* h, EncStage& s, hipStream_t st) {
     uint32_t GB = std::max<uint32_t>(1, slotsPerGroup / cpb);                   // whole blocks per group
     if (const char* e = knz_test_switch("KNZ_ANS1_GROUP_BLOCKS")) GB = std::max(1, atoi(e));   // (tests: several groups on small inputs)
     const bool ans1EncPlain = knz_test_switch("KNZ_ANS1_ENC_PLAIN") != nullptr;   // (A/B and cross-check: the compiler's loop instead of the hand-written one)
+    const bool ans1EncOneWave = knz_test_switch("KNZ_ANS1_ENC_ONE_WAVE") != nullptr;   // (A/B and cross-check: the one-wave kernel, which places its words itself)
     // a group the device has no room for (other handles, a smaller device) is halved until it fits: fewer chains side by side, same bytes
     uint32_t gs = GB * cpb;
     for (;;) {
@@ -153,11 +154,12 @@ static int ans1_encode_stage(Handle* h, EncStage& s, hipStream_t st) {
         hipLaunchKernelGGL(knz_ans1_stats_kernel, dim3(ns * 256), dim3(64), 0, st, a);
         hipLaunchKernelGGL(knz_ans1_merge_kernel, dim3(ns), dim3(256), 0, st, a);
         KNZ_LAUNCH_PROBED(knz_ans1_expand_kernel, dim3(ns, 128), dim3(256), 0, st, a, h->a1_ent.as<uint4>());
+        // two waves a chunk: one codes, one places the renormalisation words (ans1.hip); the emulator has the same two waves around the C++ step
+        if (!ans1EncPlain && !ans1EncOneWave) KNZ_LAUNCH_PROBED(knz_ans1_encode_asm_kernel, dim3(ns), dim3(128), 0, st, a, (const uint4*)h->a1_ent.as<uint4>());
 #ifndef KNZ_HIP_EMU
-        if (!ans1EncPlain) KNZ_LAUNCH_PROBED(knz_ans1_encode_asm_kernel, dim3(ns), dim3(64), 0, st, a, (const uint4*)h->a1_ent.as<uint4>());
-        else
+        else if (!ans1EncPlain) KNZ_LAUNCH_PROBED(knz_ans1_encode_asm1_kernel, dim3(ns), dim3(64), 0, st, a, (const uint4*)h->a1_ent.as<uint4>());
 #endif
-        KNZ_LAUNCH_PROBED(knz_ans1_encode_kernel, dim3(ns), dim3(64), 0, st, a, (const uint4*)h->a1_ent.as<uint4>());
+        else KNZ_LAUNCH_PROBED(knz_ans1_encode_kernel, dim3(ns), dim3(64), 0, st, a, (const uint4*)h->a1_ent.as<uint4>());
     }
     return KNZ_OK;
 }
@@ -673,6 +675,7 @@ static int dec_header_pass(Handle* h, DecStage& d, const EntropyCodec& ec, hipSt
     wb.check_out = direct ? 1 : 0; wb.out_off = h->blk_off.as<uint64_t>(); wb.out_base = (uint64_t)db.d_out; wb.out_stride = db.out_stride;
     wb.out_cap = db.out_cap; wb.stream_block_size = db.block_size;
     wb.ans1_ctx_bit = nullptr;
+    wb.ans1_walk_plain = knz_test_switch("KNZ_ANS1_WALK_PLAIN") != nullptr ? 1u : 0u;   // (A/B and cross-check: the generic reader's walk of the chunk headers)
     if (db.entropy == KNZ_E_ANS1) {                                           // the walk leaves every context header's position for the table kernel
         if (h->a1_ctxpos.reserve((size_t)nslots * 257 * 8 + 64)) return knz_set_error(h, KNZ_ERR_CREATE_DECOMPRESSOR, "device workspace allocation failed");
         wb.ans1_ctx_bit = h->a1_ctxpos.as<uint64_t>();
